@@ -29,6 +29,13 @@ The frame is fixed as N grows, so scaling is "strong".
     python bench.py [--gpus N --steps K --warmup W]      # N > 1: the library's multi-GPU render
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR`
+also writes the last timed step's frame, as the caller receives it in host memory, to
+DIR/frame.npy (float32, H x W x 3; a fixed seeded sample of the pixels, n x 3, past 64 MB):
+the scene file and the pixel-keyed RNG are the only inputs, so two builds of the library can be
+compared value for value.  `--full` adds the legs that take runs of their own: today the
+cpu_baseline leg.
+
 Rank 0 prints one JSON line.  `roofline` prices the render kernel against the
 bound that limits it, the FP32 (or FP64) VALU peak: achieved = SURVEY §8(d)'s
 algorithmic FLOPs per sample (oracle event counts x per-event costs,
@@ -36,7 +43,7 @@ tests/golden/work_counts.json) x samples per launch / the kernel's HIP-event
 time on its launch stream.  The HBM figures the north star asks for sit beside
 it (`roofline.hbm`): framebuffer + texel fetch bytes per launch over the same time,
 and rocprofv3 FETCH_SIZE/WRITE_SIZE traffic from profiles/pmc_summary.json,
-looked up by (scene, size, spp, precision, rng, trace).  The cpu_baseline leg
+looked up by (scene, size, spp, precision, rng, trace).  The cpu_baseline leg (`--full`)
 times the oracle (the C++ f64 restatement; the Rust reference cannot be built
 here), compiled for the host CPU, on every core this process may use, over a
 bounded row sample of the same frame.
@@ -233,7 +240,13 @@ def parse_args(argv=None):
     ap.add_argument("--rng", default="philox", choices=["chacha8", "philox"])
     ap.add_argument("--trace", default="auto", choices=["auto", "bvh", "world-list", "world-bvh"],
                     help="f32 kernel traversal (nrt_trace): auto = world-space list for small flattenable scenes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the CPU baseline (the oracle on the host "
+                         "cores over a row sample of the frame, `cpu_baseline` on the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's frame (host memory, float32) to "
+                         "DIR/frame.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-row-stride", type=int, default=16)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="one process per GPU: nccl = RCCL over xGMI, one GPU per rank (the measured path); gloo = "
@@ -395,11 +408,25 @@ def report(args, nrt, scene, *, n_gpus, rows, elapsed, kern_ms, d2h_ms, timings_
     }
     if extra:
         out.update(extra)
-    if not args.no_cpu_baseline and n_gpus == 1:
-        out["cpu_baseline"] = cpu_baseline(args)
-    elif not args.no_cpu_baseline:
-        out["cpu_baseline"] = None
+    if args.full and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args) if n_gpus == 1 else None
     print(json.dumps(out), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname, frame):
+    """--dump-outputs: the frame the timed path left in host memory (H x W x 3 float32) as DIR/frame.npy;
+    past DUMP_LIMIT_BYTES a fixed, seeded sample of its pixels in index order (n x 3)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(frame, dtype=np.float32)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        px = a.reshape(-1, 3)
+        a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_LIMIT_BYTES // 12, replace=False))]
+    np.save(os.path.join(dirname, "frame.npy"), a)
 
 
 def run_library(args):
@@ -471,6 +498,8 @@ def run_library(args):
     jit_after = nrt.jit_stats()
     last = host[(args.warmup + args.steps - 1) % NB].numpy()
     frame_sha = None if args.kernel_only else hashlib.sha256(last.tobytes()).hexdigest()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     rows = scene.rows_selected(H, 0, N)
     # the device time per timed frame: GPU 0's first timed render start to the last frame's completion, over
     # the frames (the renders overlap at their ends, as with --pipeline > 1)
@@ -494,6 +523,8 @@ def run_library(args):
 
 def main():
     args = parse_args()
+    if args.dump_outputs and args.kernel_only:
+        raise SystemExit("bench.py: --kernel-only leaves no frame in host memory for --dump-outputs")
     if os.environ.get("NRT_MULTI_LOOPBACK", "0") not in ("", "0") and not os.environ.get("NRT_BENCH_DIAG_LOOPBACK"):
         # the library's test-only loopback (every shard of a gpus = N render on GPU 0, the gather as
         # device copies) would time N shards on one GPU as an N-GPU line: never a measurement
@@ -694,6 +725,8 @@ def run_ranks(args):
     if lead:
         last = host[(args.warmup + args.steps - 1) % NB].numpy()
         frame_sha = None if args.kernel_only else hashlib.sha256(last.tobytes()).hexdigest()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last)
         report(args, nrt, scene, n_gpus=world, rows=rows, elapsed=elapsed, kern_ms=kern_ms, d2h_ms=d2h_ms,
                timings_s={"runtime_init": round(t_init, 4), "scene_load_and_bvh": round(t_load, 4),
                           "upload": round(t_upload, 4), "jit_compile": jit_after["compile_s"],

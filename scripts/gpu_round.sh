@@ -13,5 +13,6 @@ done
 bash scripts/configs_bench.sh ${tag}_cfg || exit 1
 timeout -k 10 200 python scripts/phase_profile.py scenes/cornell-box-scene.json f32/philox/auto f32/chacha8/auto > gpurun_out/${tag}_phase.json 2>/dev/null || exit 1
 timeout -k 10 200 python scripts/shard_timing.py > gpurun_out/${tag}_shard_c5.json 2>/dev/null || exit 1
-timeout -k 10 300 python bench.py > gpurun_out/${tag}_bench_default.json 2> gpurun_out/${tag}_bench_default.err || exit 1
+out=${NRT_OUT:-out}; mkdir -p "$out"  # the default line, with the CPU baseline (--full)
+timeout -k 10 300 python bench.py --full > "$out/${tag}_bench_default.json" 2> "$out/${tag}_bench_default.err" || exit 1
 echo done

@@ -2,16 +2,15 @@
 the cited reference file (a restatement that cites line ranges that do
 not exist cannot be audited).  Paths may be abbreviated to a suffix of the real path;
 `lib/` = packages/ray-tracer-lib/src/, `app/` = packages/ray-tracer/src/ (DESIGN.md).
-Skipped where /root/reference is absent (the GPU box)."""
+The reference files' line counts are the fixture tests/golden/reference_rs_lines.json
+(scripts/make_reference_lines.py records them from a checkout of the reference)."""
 import collections
+import json
 import os
 import re
 
-import pytest
+from helpers import GOLDEN, ROOT
 
-from helpers import ROOT
-
-REF = "/root/reference"
 PAT = re.compile(r"((?:[A-Za-z_]+/)*[A-Za-z_\-]+\.rs):(\d+)(?:-(\d+))?")
 EXTS = (".py", ".cpp", ".hpp", ".hip", ".h", ".md", ".sh", "Makefile")
 SKIP_DOCS = {"SURVEY.md", "VERDICT.md", "ADVICE.md", "BASELINE.md", "PAPERS.md", "SNIPPETS.md"}  # not ours
@@ -19,12 +18,9 @@ SKIP_DOCS = {"SURVEY.md", "VERDICT.md", "ADVICE.md", "BASELINE.md", "PAPERS.md",
 
 def _reference_files():
     files = collections.defaultdict(list)
-    for dp, _, fs in os.walk(REF):
-        for f in fs:
-            if f.endswith(".rs"):
-                p = os.path.join(dp, f)
-                with open(p, errors="replace") as fh:
-                    files[f].append((p, sum(1 for _ in fh)))
+    with open(os.path.join(GOLDEN, "reference_rs_lines.json")) as fh:
+        for p, n in json.load(fh)["lines"].items():
+            files[os.path.basename(p)].append(("/" + p, n))
     return files
 
 
@@ -36,7 +32,6 @@ def _expand(path):
     return path
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources not present")
 def test_every_reference_citation_is_in_range():
     files = _reference_files()
     bad, seen = [], 0

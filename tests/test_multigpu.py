@@ -107,6 +107,21 @@ def test_bench_multirank_step_matches_single(precision, rng):
     assert one["frame_sha256"] and two["frame_sha256"] == one["frame_sha256"]
 
 
+def test_bench_dump_outputs_is_the_timed_frame(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed frame (the one `frame_sha256` is taken of) to
+    DIR/frame.npy, the same values from run to run; a plain run leaves the CPU baseline to --full."""
+    import hashlib
+    one = _bench(1, ("--dump-outputs", str(tmp_path / "a")))
+    two = _bench(1, ("--dump-outputs", str(tmp_path / "b"), "--steps", "3"))
+    a, b = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "b" / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (H, W, 3)
+    assert hashlib.sha256(a.tobytes()).hexdigest() == one["frame_sha256"]
+    np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(a, _single()[0])
+    assert one["steps"] == 2 and two["steps"] == 3 and one["ms_per_step"] > 0
+    assert "cpu_baseline" not in one
+
+
 def test_bench_without_launcher_starts_its_ranks():
     """`python bench.py --gpus 2 --backend gloo` with no launcher (as a driver might invoke it): bench.py
     starts torch.distributed.run as a child process and forwards its line; the frame equals N = 1."""

@@ -62,6 +62,32 @@ def test_bench_work_block():
     assert c3["name"] == "C3" and c3["per_sample"]["texel_fetches"] > 0.2
 
 
+def test_bench_dump_outputs_and_full_options(tmp_path, monkeypatch):
+    """--dump-outputs writes the frame as it is (float32, H x W x 3), and past the size limit a fixed
+    sample of its pixels, the same from call to call; the CPU baseline runs only with --full."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse_args([])
+    assert not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    frame = np.random.default_rng(1).random((37, 64, 3), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "whole"), frame)
+    got = np.load(tmp_path / "whole" / "frame.npy")
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, frame)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1200)
+    bench.dump_outputs(str(tmp_path / "s1"), frame)
+    bench.dump_outputs(str(tmp_path / "s2"), frame)
+    s1, s2 = np.load(tmp_path / "s1" / "frame.npy"), np.load(tmp_path / "s2" / "frame.npy")
+    assert s1.shape == (100, 3) and s1.nbytes <= 1200
+    np.testing.assert_array_equal(s1, s2)
+    assert set(map(tuple, s1)) <= set(map(tuple, frame.reshape(-1, 3)))
+
+
 def test_bench_chooses_the_n_gpu_path():
     """bench.py --gpus N as a driver may invoke it: without a launcher and with RCCL the library's
     multi-GPU render (one process); with --backend gloo, or under torch.distributed.run, one process
