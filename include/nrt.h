@@ -274,6 +274,49 @@ int nrt_render_prepare(const nrt_scene* scene, const nrt_camera* camera, const n
  * frame's completion (gather + un-permute done), over the frames (0 with fewer than two); a call that
  * writes out[N+1] starts a new window.  *count = N + 2; at most n written. */
 int nrt_render_timings(const nrt_scene* scene, float* out, size_t n, size_t* count);
+/* ---- feature buffers and the edge-avoiding filter (reference counterpart: none; the reference
+ *      writes the Monte-Carlo frame as it is) */
+typedef struct {
+    uint32_t iterations; /* a-trous passes K, 1..5; 0 = 5.  Pass i has step 2^i */
+    float sigma_color, sigma_normal, sigma_depth; /* <= 0: the defaults 0.6, 0.3, 0.5 */
+} nrt_denoise_opts;
+/* First-hit feature buffers of the rows opts selects (reference counterpart: none): one primary
+ * ray per pixel, origin look_from, direction top_left + x pixel_delta_u + y pixel_delta_v -
+ * look_from (no jitter, no defocus, time 0), traced in f32 in the mode opts->trace names (AUTO as
+ * the render; precision and rng are not read).  albedo, normal: 3 f32 per pixel, depth: 1, row-major,
+ * each with room for n_pixels >= rows * width pixels; any of the three may be NULL.
+ *   albedo  Lambertian / Metal / DiffuseLight: the texture's colour at the hit (a light's is not
+ *           scaled by its intensity); Dielectric: (1, 1, 1); miss: the camera's background colour
+ *   normal  the hit record's unit normal, facing the ray; miss: (0, 0, 0)
+ *   depth   distance from look_from to the hit point; miss: 0 (no hit has it: t >= 0.001)
+ * Host buffers, synchronous.  opts->gpus >= 1: NRT_E_INVALID (one device renders the pass). */
+int nrt_render_aov(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts, float* albedo,
+                   float* normal, float* depth, size_t n_pixels);
+/* Same, into device memory on `hip_stream` (NULL = default stream); asynchronous (reference
+ * counterpart: none). */
+int nrt_render_aov_device(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                          float* dev_albedo, float* dev_normal, float* dev_depth, size_t n_pixels, void* hip_stream);
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of a `rows` x `width` frame (reference
+ * counterpart: none).  With a = max(albedo, 1e-3), D_0 = colour / a, and for pass i = 0 .. K-1 the
+ * step s = 2^i, taps q = p + s (dx, dy) with dx, dy in -2 .. 2 (those outside the image skipped) and
+ * h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *   e(p, q) = |D_i(p) - D_i(q)|^2 / (sigma_color 2^-i)^2 + |N(p) - N(q)|^2 / sigma_normal^2
+ *             + (Z(p) - Z(q))^2 / sigma_depth^2
+ *   D_{i+1}(p) = sum_q h[dx] h[dy] exp(-e) D_i(q) / sum_q h[dx] h[dy] exp(-e)
+ * out = D_K a.  colour, albedo, normal, out: 3 f32 per pixel, depth: 1; out may be colour (in
+ * place), no other overlap.  dopts NULL = the defaults.  The result is a pure function of the
+ * inputs, the same bits from run to run.  Needs no scene: host buffers, device scratch for the
+ * call's duration on `device` (-1 = the current device), synchronous. */
+int nrt_denoise(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
+                uint32_t rows, const nrt_denoise_opts* dopts, int32_t device, float* out);
+/* Same over device memory on the device that holds it (`device`, -1 = current), K launches enqueued on
+ * `hip_stream`, asynchronous (reference counterpart: none).  The scene owns the scratch (two colour
+ * buffers and the packed guide records, 40 B per pixel; created on first use, kept for the next
+ * frame, freed with the scene): calls on one scene and device must be ordered by their streams. */
+int nrt_denoise_device(const nrt_scene* scene, const float* dev_colour, const float* dev_albedo,
+                       const float* dev_normal, const float* dev_depth, uint32_t width, uint32_t rows,
+                       const nrt_denoise_opts* dopts, int32_t device, float* dev_out, void* hip_stream);
+
 /* Number of rows selected by opts for an image of `height` rows. */
 uint32_t nrt_rows_selected(uint32_t height, const nrt_render_opts* opts);
 /* Upload the flattened scene to `device` now (otherwise done on first render). */

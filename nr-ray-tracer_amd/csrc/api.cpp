@@ -28,7 +28,9 @@ struct nrt_scene {
     // multi-GPU renders (nrt_render_opts.gpus): one context per (first device, N, loopback), the last used
     std::map<std::tuple<int, int, bool>, MultiRender*> multi;
     MultiRender* last_multi = nullptr;
+    std::vector<DenoiseScratch*> denoise;  // the filter's scratch (nrt_denoise_device), index = HIP ordinal
     ~nrt_scene() {
+        for (DenoiseScratch* d : denoise) gpu_denoise_scratch_free(d);
         for (auto& kv : multi) gpu_multi_free(kv.second);  // (before the device scenes they render)
         for (DeviceScene* d : per_device) gpu_free_scene(d);
     }
@@ -403,6 +405,7 @@ namespace nrt {
 void* device_alloc(size_t bytes, int device);
 void device_free(void* p, int device);
 void device_copy_to_host(void* dst, const void* src, size_t bytes, int device);
+void device_copy_from_host(void* dst, const void* src, size_t bytes, int device);
 void device_sync(int device);
 void device_zero(void* p, size_t bytes, int device);
 }
@@ -687,6 +690,146 @@ int nrt_render(const nrt_scene* scene, const nrt_camera* camera, const nrt_rende
             device_free(d, dev);
             throw;
         }
+        device_free(d, dev);
+        return NRT_OK;
+    });
+}
+
+// ---- feature buffers (aov.hip) and the a-trous filter (denoise.hip)
+namespace {
+
+struct DenoiseArgs {
+    uint32_t iterations;
+    float sigma_color, sigma_normal, sigma_depth;
+};
+
+DenoiseArgs denoise_args(const void* c, const void* a, const void* n, const void* z, const void* out, uint32_t width,
+                         uint32_t rows, const nrt_denoise_opts* o) {
+    if (!c || !a || !n || !z || !out) throw std::invalid_argument("null argument");
+    // (the lattice grid of step 16 has rows / 8 + 16 workgroup rows: below HIP's 65 536)
+    if (width == 0 || rows == 0 || width > (1u << 24) || rows > (1u << 18))
+        throw std::invalid_argument("denoise: width in 1..2^24 and rows in 1..2^18");
+    DenoiseArgs d{5u, 0.6f, 0.3f, 0.5f};
+    if (o) {
+        if (o->iterations > 5) throw std::invalid_argument("denoise: iterations must be 1..5 (0 = 5)");
+        if (o->iterations) d.iterations = o->iterations;
+        if (o->sigma_color > 0.0f) d.sigma_color = o->sigma_color;
+        if (o->sigma_normal > 0.0f) d.sigma_normal = o->sigma_normal;
+        if (o->sigma_depth > 0.0f) d.sigma_depth = o->sigma_depth;
+    }
+    return d;
+}
+
+int device_or_current(int32_t device) {
+    nrt_render_opts o{};
+    o.device = device;
+    return resolve_device(&o);
+}
+
+// Checks shared by the two feature-pass calls; the launch parameters of the rows opts selects.
+RenderParams aov_params(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                        size_t n_pixels) {
+    if (!scene || !camera) throw std::invalid_argument("null argument");
+    check_opts(opts);
+    if (opts && opts->gpus) throw std::invalid_argument("the feature pass runs on one device: gpus must be 0");
+    const uint32_t rows = rows_selected((uint32_t)camera->height, opts);
+    nrt_render_opts o = opts ? *opts : nrt_render_opts{};
+    if (!opts) o.device = -1;
+    o.precision = NRT_PRECISION_F32;  // (the camera's f32 copy; no sample pool is sized)
+    o.rng = NRT_RNG_CHACHA8;
+    RenderParams p = make_params(*camera, &o, rows, scene->flat);
+    if (n_pixels < (size_t)rows * p.width) throw std::invalid_argument("feature buffers too small");
+    return p;
+}
+
+}  // namespace
+
+int nrt_render_aov_device(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                          float* dev_albedo, float* dev_normal, float* dev_depth, size_t n_pixels, void* hip_stream) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        const RenderParams p = aov_params(scene, camera, opts, n_pixels);
+        const int dev = resolve_device(opts);
+        DeviceScene* ds = device_scene(const_cast<nrt_scene*>(scene), dev);
+        gpu_launch_aov(ds, p, opts ? opts->trace : 0, dev_albedo, dev_normal, dev_depth, hip_stream);
+        return NRT_OK;
+    });
+}
+
+int nrt_render_aov(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts, float* albedo,
+                   float* normal, float* depth, size_t n_pixels) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        const RenderParams p = aov_params(scene, camera, opts, n_pixels);
+        const size_t n = (size_t)p.rows * p.width;
+        if (n == 0) return NRT_OK;
+        const int dev = resolve_device(opts);
+        DeviceScene* ds = device_scene(const_cast<nrt_scene*>(scene), dev);
+        float* d = (float*)device_alloc(n * 7 * sizeof(float), dev);  // albedo | normal | depth
+        try {
+            gpu_launch_aov(ds, p, opts ? opts->trace : 0, albedo ? d : nullptr, normal ? d + 3 * n : nullptr,
+                           depth ? d + 6 * n : nullptr, nullptr);
+            device_sync(dev);
+            if (albedo) device_copy_to_host(albedo, d, n * 3 * sizeof(float), dev);
+            if (normal) device_copy_to_host(normal, d + 3 * n, n * 3 * sizeof(float), dev);
+            if (depth) device_copy_to_host(depth, d + 6 * n, n * sizeof(float), dev);
+        } catch (...) {
+            device_free(d, dev);
+            throw;
+        }
+        device_free(d, dev);
+        return NRT_OK;
+    });
+}
+
+int nrt_denoise_device(const nrt_scene* scene, const float* dev_colour, const float* dev_albedo,
+                       const float* dev_normal, const float* dev_depth, uint32_t width, uint32_t rows,
+                       const nrt_denoise_opts* dopts, int32_t device, float* dev_out, void* hip_stream) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        if (!scene) throw std::invalid_argument("null argument");
+        const DenoiseArgs a = denoise_args(dev_colour, dev_albedo, dev_normal, dev_depth, dev_out, width, rows, dopts);
+        const int dev = device_or_current(device);
+        nrt_scene* s = const_cast<nrt_scene*>(scene);
+        DenoiseScratch* scratch = nullptr;
+        {
+            std::lock_guard<std::mutex> lock(s->mu);
+            if ((int)s->denoise.size() <= dev) s->denoise.resize((size_t)dev + 1, nullptr);
+            DenoiseScratch*& slot = s->denoise[(size_t)dev];
+            DenoiseScratch* have = slot;
+            slot = nullptr;  // (gpu_denoise_scratch frees `have` before it can throw)
+            scratch = slot = gpu_denoise_scratch(have, (size_t)width * rows, dev);
+        }
+        gpu_denoise(scratch, dev_colour, dev_albedo, dev_normal, dev_depth, width, rows, a.iterations, a.sigma_color,
+                    a.sigma_normal, a.sigma_depth, dev_out, hip_stream);
+        return NRT_OK;
+    });
+}
+
+int nrt_denoise(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
+                uint32_t rows, const nrt_denoise_opts* dopts, int32_t device, float* out) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        const DenoiseArgs a = denoise_args(colour, albedo, normal, depth, out, width, rows, dopts);
+        const int dev = device_or_current(device);
+        const size_t n = (size_t)width * rows;
+        float* d = nullptr;  // colour | albedo | normal | depth | out (out == colour: filtered in place)
+        DenoiseScratch* scratch = nullptr;
+        const bool in_place = out == colour;
+        try {
+            d = (float*)device_alloc(n * (in_place ? 10 : 13) * sizeof(float), dev);
+            float* const dout = in_place ? d : d + 10 * n;
+            scratch = gpu_denoise_scratch(nullptr, n, dev);
+            device_copy_from_host(d, colour, n * 3 * sizeof(float), dev);
+            device_copy_from_host(d + 3 * n, albedo, n * 3 * sizeof(float), dev);
+            device_copy_from_host(d + 6 * n, normal, n * 3 * sizeof(float), dev);
+            device_copy_from_host(d + 9 * n, depth, n * sizeof(float), dev);
+            gpu_denoise(scratch, d, d + 3 * n, d + 6 * n, d + 9 * n, width, rows, a.iterations, a.sigma_color,
+                        a.sigma_normal, a.sigma_depth, dout, nullptr);
+            device_sync(dev);
+            device_copy_to_host(out, dout, n * 3 * sizeof(float), dev);
+        } catch (...) {
+            gpu_denoise_scratch_free(scratch);
+            if (d) device_free(d, dev);
+            throw;
+        }
+        gpu_denoise_scratch_free(scratch);
         device_free(d, dev);
         return NRT_OK;
     });

@@ -3,7 +3,8 @@
 // same flags and NR_RT_CAMERA_* environment variables, render timed alone
 // (render.rs:57-62), gamma 0.5 + to_rgb8 + write (render.rs:74-102).
 // Extra flags: --precision {f64,f32}, --rng {chacha8,philox}, --gpus N, --legacy-schema (also
-// load the index schema of scenes/triangles.toml, NRT_LOAD_LEGACY_SCHEMA).
+// load the index schema of scenes/triangles.toml, NRT_LOAD_LEGACY_SCHEMA), --denoise[=K] (the
+// a-trous filter over the frame and its first-hit feature buffers, K = 1..5 passes, default 5).
 // Output formats: .png (stored deflate), .ppm, .pfm (linear f32).
 //
 // `nrt-cli convert-stl <STL> [-o FILE] [-f] [-F toml|json]` — the reference's
@@ -217,7 +218,7 @@ void usage() {
             "       [--background-color X,Y,Z] [--look-at X,Y,Z] [--look-from X,Y,Z] [--view-up X,Y,Z]\n"
             "       [--focal-length F] [--field-of-view DEG] [--defocus-angle DEG] [--focus-distance D]\n"
             "       [--samples-per-pixel N] [--ray-max-bounces N] [-v]\n"
-            "       [--precision f64|f32] [--rng chacha8|philox] [--gpus N] [--legacy-schema]\n");
+            "       [--precision f64|f32] [--rng chacha8|philox] [--gpus N] [--legacy-schema] [--denoise[=K]]\n");
     exit(2);
 }
 
@@ -231,6 +232,7 @@ int main(int argc, char** argv) {
     uint32_t load_flags = 0;
     float gamma = 0.5f;
     int gpus = 1;
+    uint32_t denoise = 0;  // a-trous passes (0: no filter)
     nrt_camera_config cc{};
     nrt_render_opts opts{};
     opts.device = -1;
@@ -271,6 +273,11 @@ int main(int argc, char** argv) {
             if (opts.rng == 99) die("--rng must be chacha8 or philox");
         } else if (a == "--gpus") gpus = atoi(val().c_str());
         else if (a == "--legacy-schema") load_flags |= NRT_LOAD_LEGACY_SCHEMA;  // a switch: takes no value
+        else if (a == "--denoise") denoise = 5;
+        else if (a.rfind("--denoise=", 0) == 0) {
+            denoise = (uint32_t)atoi(a.c_str() + 10);
+            if (denoise < 1 || denoise > 5) die("--denoise=K: K must be 1..5");
+        }
         else if (a.rfind("--", 0) == 0) kv.emplace_back(a, val());
         else if (scene.empty()) scene = a;
         else usage();
@@ -376,6 +383,22 @@ int main(int argc, char** argv) {
         die(nrt_last_error());
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (denoise) {  // before the output stage: feature buffers on the first device, the frame filtered in place
+        const auto td = std::chrono::steady_clock::now();
+        const size_t n = (size_t)W * H;
+        std::vector<float> albedo(n * 3), normal(n * 3), depth(n);
+        nrt_render_opts ao = opts;
+        ao.gpus = 0;
+        ao.device = gpus > 1 ? dev_of(0) : opts.device;
+        nrt_denoise_opts dopts{};
+        dopts.iterations = denoise;
+        if (nrt_render_aov(sc, &cam, &ao, albedo.data(), normal.data(), depth.data(), n) != NRT_OK ||
+            nrt_denoise(img.data(), albedo.data(), normal.data(), depth.data(), W, H, &dopts, ao.device, img.data()) != NRT_OK)
+            die(nrt_last_error());
+        if (verbose)
+            fprintf(stderr, " Denoising (%u passes) - Done in %.3f secs\n", denoise,
+                    std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count());
+    }
     if (verbose) {
         const double samples = (double)W * H * (double)cam.samples_per_pixel;
         fprintf(stderr, " GPU runtime start + scene upload: %.3f secs\n", init_secs);

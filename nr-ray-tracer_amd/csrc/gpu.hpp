@@ -46,6 +46,20 @@ void gpu_launch_render(const DeviceScene* ds, const RenderParams& p, uint32_t pr
                        void* stream);
 // f32 kernel mode for nrt_trace `trace`: 0 = world-space list, 1 / MAX_INSTANCE_DEPTH = instance BVH.
 int gpu_fast_maxd(const DeviceScene* ds, uint32_t trace);
+// Enqueue the feature-buffer pass (aov.hip) on `stream`: first-hit albedo / normal (3 f32 per pixel) and
+// depth (1 f32) of the rows p selects, device pointers, any of them null; traversal as the f32 render's.
+void gpu_launch_aov(const DeviceScene* ds, const RenderParams& p, uint32_t trace, float* albedo, float* normal,
+                    float* depth, void* stream);
+// A-trous filter (denoise.hip).  The scratch (two colour buffers and the packed guide records) holds
+// `pixels` pixels on `device`; gpu_denoise_scratch returns `have` when it is large enough, else frees it
+// and allocates anew (have may be null).
+struct DenoiseScratch;
+DenoiseScratch* gpu_denoise_scratch(DenoiseScratch* have, size_t pixels, int device);  // throws
+void gpu_denoise_scratch_free(DenoiseScratch* s);
+// Enqueue the `iterations` passes on `stream` (device pointers; out may be colour); sigmas > 0.
+void gpu_denoise(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
+                 uint32_t width, uint32_t rows, uint32_t iterations, float sigma_color, float sigma_normal,
+                 float sigma_depth, float* out, void* stream);
 // First `count` draws of `lanes` consecutive streams starting at stream0 (tests).
 struct JitCounts {
     uint64_t compiled, launches, failed, compile_ns, disk_hits, load_retries;

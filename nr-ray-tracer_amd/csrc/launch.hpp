@@ -24,6 +24,10 @@ void launch_exact(const RenderParams& p, const DSceneView<double>& v, uint32_t r
                   bool planes, hipStream_t stream);
 void launch_fast(const RenderParams& p, const DSceneView<float>& v, uint32_t rng, int maxd, bool perlin, bool flat,
                  hipStream_t stream);
+// Feature buffers of the first hit (aov.hip): one primary ray per pixel of [p.pixel_begin, p.pixel_end) in
+// the f32 mode maxd, into albedo / normal (3 f32 per pixel) and depth (1); any of them may be null.
+void launch_aov(const RenderParams& p, const DSceneView<float>& v, int maxd, bool perlin, float* albedo, float* normal,
+                float* depth, hipStream_t stream);
 // Scenes whose node/prim/xform/material tables fit stay in LDS for the whole launch.
 constexpr uint32_t LDS_SCENE_LIMIT = 64 * 1024;
 

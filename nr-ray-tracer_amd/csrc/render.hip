@@ -254,6 +254,33 @@ int gpu_fast_maxd(const DeviceScene* ds, uint32_t trace) {
     return ds->wbvh_ok ? MODE_WORLD_BVH : inst_maxd;
 }
 
+// The f32 view of mode maxd: only the tables the mode reads are staged (LDS).
+static DSceneView<float> mode_view(const DeviceScene* ds, int maxd) {
+    DSceneView<float> v = ds->v32;
+    if (maxd == MODE_WORLD_LIST) {
+        v.n_nodes = v.n_fprims = v.n_inst_fast = v.n_instances = 0;
+    } else if (maxd == MODE_WORLD_BVH) {
+        v.n_nodes = v.n_fprims = v.n_inst_fast = v.n_instances = 0;
+        v.wprims = ds->wbvh_prims;  // records come from the BVH-ordered array
+        v.n_wprims = ds->n_wbvh_prims;
+        v.wruns = nullptr;
+        v.n_wruns = 0;
+    } else {
+        v.n_wprims = 0;
+    }
+    return v;
+}
+
+void gpu_launch_aov(const DeviceScene* ds, const RenderParams& p, uint32_t trace, float* albedo, float* normal,
+                    float* depth, void* stream_ptr) {
+    if (p.pixel_end <= p.pixel_begin) return;
+    if (p.width == 0) throw std::runtime_error("width must be > 0");
+    DeviceGuard guard(ds->device);
+    const int maxd = gpu_fast_maxd(ds, trace);
+    launch_aov(p, mode_view(ds, maxd), maxd, ds->perlin, albedo, normal, depth, (hipStream_t)stream_ptr);
+    check(hipGetLastError(), "feature-buffer kernel launch");
+}
+
 void gpu_launch_render(const DeviceScene* ds, const RenderParams& p, uint32_t precision, uint32_t rng,
                        uint32_t trace, void* stream_ptr) {
     if (p.pixel_end <= p.pixel_begin) return;
@@ -285,18 +312,7 @@ void gpu_launch_render(const DeviceScene* ds, const RenderParams& p, uint32_t pr
         launch_exact(q, ds->v64, rng, ds->v64.max_depth > 1 ? MAX_INSTANCE_DEPTH : 1, ds->perlin, ds->planes, stream);
     else {
         const int maxd = gpu_fast_maxd(ds, trace);
-        DSceneView<float> v = ds->v32;  // stage (LDS) only the tables this mode reads
-        if (maxd == MODE_WORLD_LIST) {
-            v.n_nodes = v.n_fprims = v.n_inst_fast = v.n_instances = 0;
-        } else if (maxd == MODE_WORLD_BVH) {
-            v.n_nodes = v.n_fprims = v.n_inst_fast = v.n_instances = 0;
-            v.wprims = ds->wbvh_prims;  // records come from the BVH-ordered array
-            v.n_wprims = ds->n_wbvh_prims;
-            v.wruns = nullptr;
-            v.n_wruns = 0;
-        } else {
-            v.n_wprims = 0;
-        }
+        const DSceneView<float> v = mode_view(ds, maxd);
         // scene-specialised kernel (jit.hip): the world list's run words, or the world BVH's
         // width and tie flag, as template arguments; the same LDS layout as launch_one
         void* jit = nullptr;
@@ -376,6 +392,10 @@ void device_free(void* p, int device) {
 void device_copy_to_host(void* dst, const void* src, size_t bytes, int device) {
     DeviceGuard guard(device);
     check(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "hipMemcpy(output)");
+}
+void device_copy_from_host(void* dst, const void* src, size_t bytes, int device) {
+    DeviceGuard guard(device);
+    check(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(input)");
 }
 void device_zero(void* p, size_t bytes, int device) {
     DeviceGuard guard(device);

@@ -73,6 +73,11 @@ class _SceneStats(C.Structure):
                 ("texel_formats", C.c_uint32), ("texel_bytes", C.c_uint64)]
 
 
+class _DenoiseOpts(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64)
 
 # Every symbol include/nrt.h declares, with its ctypes signature.
@@ -122,6 +127,14 @@ SIGNATURES = {
                                     C.c_void_p]),
     "nrt_render_prepare": (C.c_int, [C.c_void_p, C.POINTER(_Camera), C.POINTER(_RenderOpts)]),
     "nrt_render_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "nrt_render_aov": (C.c_int, [C.c_void_p, C.POINTER(_Camera), C.POINTER(_RenderOpts), C.POINTER(C.c_float),
+                                 C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]),
+    "nrt_render_aov_device": (C.c_int, [C.c_void_p, C.POINTER(_Camera), C.POINTER(_RenderOpts), C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nrt_denoise": (C.c_int, [C.POINTER(C.c_float)] * 4 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseOpts), C.c_int32,
+                              C.POINTER(C.c_float)]),
+    "nrt_denoise_device": (C.c_int, [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseOpts), C.c_int32,
+                                     C.c_void_p, C.c_void_p]),
     "nrt_rows_selected": (C.c_uint32, [C.c_uint32, C.POINTER(_RenderOpts)]),
     "nrt_scene_upload": (C.c_int, [C.c_void_p, C.c_int32]),
     "nrt_scene_stats_get": (C.c_int, [C.c_void_p, C.POINTER(_SceneStats)]),
@@ -405,12 +418,22 @@ class Scene:
 
     def render(self, camera: Optional[Camera] = None, precision: str = "f64", rng: str = "chacha8",
                device: int = -1, row_offset: int = 0, row_stride: int = 1,
-               progress: Optional[Callable[[int], None]] = None, trace: str = "auto", gpus: int = 0) -> np.ndarray:
+               progress: Optional[Callable[[int], None]] = None, trace: str = "auto", gpus: int = 0,
+               denoise=False) -> np.ndarray:
         """Camera::render -> Rgb32FImage as float32 array (rows, W, 3).  gpus = N >= 1: the whole frame
-        over devices device .. device+N-1 (device -1: 0), one RCCL gather (nrt_render_opts.gpus)."""
+        over devices device .. device+N-1 (device -1: 0), one RCCL gather (nrt_render_opts.gpus).
+        denoise = True (or the number of passes, 1..5): the frame, then its feature buffers
+        (render_aov), then the a-trous filter (nrt.denoise) over both; whole frames on one device."""
         cam = camera or self.camera
         if cam is None:
             raise ValueError("no camera")
+        if denoise:
+            if row_stride > 1 or row_offset:
+                raise ValueError("denoise filters whole frames: row_offset 0 and row_stride 1")
+            frame = self.render(cam, precision, rng, device, progress=progress, trace=trace, gpus=gpus)
+            aov = self.render_aov(cam, trace=trace, device=device)
+            return globals()["denoise"](frame, iterations=5 if denoise is True else int(denoise), device=device,
+                                        out=frame, **aov)
         o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus)
         rows = lib().nrt_rows_selected(cam.height, C.byref(o))
         out = np.empty((rows, cam.width, 3), dtype=np.float32)
@@ -418,6 +441,43 @@ class Scene:
         _check(lib().nrt_render(self._h, C.byref(cam._c()), C.byref(o),
                                 out.ctypes.data_as(C.POINTER(C.c_float)), out.size, cb, None))
         return out
+
+    def render_aov(self, camera: Optional[Camera] = None, trace: str = "auto", device: int = -1,
+                   row_offset: int = 0, row_stride: int = 1, gpus: int = 0) -> dict:
+        """First-hit feature buffers (nrt_render_aov): {"albedo": (rows, W, 3), "normal": (rows, W, 3),
+        "depth": (rows, W)} float32, of the un-jittered primary ray of each pixel.  One device renders
+        the pass: gpus >= 1 is an invalid argument."""
+        cam = camera or self.camera
+        if cam is None:
+            raise ValueError("no camera")
+        o = _opts("f32", "philox", device, row_offset, row_stride, trace, gpus)
+        rows = lib().nrt_rows_selected(cam.height, C.byref(o))
+        out = {"albedo": np.empty((rows, cam.width, 3), dtype=np.float32),
+               "normal": np.empty((rows, cam.width, 3), dtype=np.float32),
+               "depth": np.empty((rows, cam.width), dtype=np.float32)}
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        _check(lib().nrt_render_aov(self._h, C.byref(cam._c()), C.byref(o), ptr(out["albedo"]), ptr(out["normal"]),
+                                    ptr(out["depth"]), rows * cam.width))
+        return out
+
+    def render_aov_device(self, albedo_ptr: int, normal_ptr: int, depth_ptr: int, n_pixels: int,
+                          camera: Optional[Camera] = None, trace: str = "auto", device: int = -1,
+                          row_offset: int = 0, row_stride: int = 1, stream: int = 0) -> None:
+        """Enqueue the feature pass into device memory (nrt_render_aov_device); a pointer may be 0."""
+        cam = camera or self.camera
+        o = _opts("f32", "philox", device, row_offset, row_stride, trace)
+        _check(lib().nrt_render_aov_device(self._h, C.byref(cam._c()), C.byref(o), C.c_void_p(albedo_ptr),
+                                           C.c_void_p(normal_ptr), C.c_void_p(depth_ptr), n_pixels, C.c_void_p(stream)))
+
+    def denoise_device(self, colour_ptr: int, albedo_ptr: int, normal_ptr: int, depth_ptr: int, width: int, rows: int,
+                       out_ptr: int, iterations: int = 5, sigma_color: float = 0.6, sigma_normal: float = 0.3,
+                       sigma_depth: float = 0.5, device: int = -1, stream: int = 0) -> None:
+        """Enqueue the a-trous filter over device memory (nrt_denoise_device; the scene owns the scratch);
+        out_ptr may be colour_ptr."""
+        d = _DenoiseOpts(iterations, sigma_color, sigma_normal, sigma_depth)
+        _check(lib().nrt_denoise_device(self._h, C.c_void_p(colour_ptr), C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr),
+                                        C.c_void_p(depth_ptr), width, rows, C.byref(d), device, C.c_void_p(out_ptr),
+                                        C.c_void_p(stream)))
 
     def phase_profile(self, camera: Optional[Camera] = None, precision: str = "f32", rng: str = "philox",
                       device: int = -1, trace: str = "auto") -> dict:
@@ -577,6 +637,28 @@ def to_rgb8(img: np.ndarray, gamma: float = 0.5) -> np.ndarray:
     out = np.empty(a.shape, dtype=np.uint8)
     _check(lib().nrt_image_to_rgb8(a.ctypes.data_as(C.POINTER(C.c_float)), a.size, gamma,
                                    out.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out
+
+
+def denoise(colour: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth: np.ndarray, iterations: int = 5,
+            sigma_color: float = 0.6, sigma_normal: float = 0.3, sigma_depth: float = 0.5, device: int = -1,
+            out: Optional[np.ndarray] = None) -> np.ndarray:
+    """Edge-avoiding a-trous filter (nrt_denoise) of a (rows, W, 3) frame with its feature buffers (albedo and
+    normal (rows, W, 3), depth (rows, W)); `out` may be `colour` (in place).  Needs no scene."""
+    def f32(a):
+        return a if a.dtype == np.float32 and a.flags.c_contiguous else np.ascontiguousarray(a, dtype=np.float32)
+
+    c, a, n, z = f32(colour), f32(albedo), f32(normal), f32(depth)
+    if c.ndim != 3 or c.shape[2] != 3 or a.shape != c.shape or n.shape != c.shape or z.shape != c.shape[:2]:
+        raise NrtError(-1, f"denoise: colour {c.shape}, albedo {a.shape}, normal {n.shape}, depth {z.shape} do not "
+                           "describe one (rows, W, 3) frame")
+    if out is None:
+        out = np.empty_like(c)
+    elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != c.shape:
+        raise NrtError(-1, "denoise: out must be a contiguous float32 array of the frame's shape")
+    d = _DenoiseOpts(iterations, sigma_color, sigma_normal, sigma_depth)
+    ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    _check(lib().nrt_denoise(ptr(c), ptr(a), ptr(n), ptr(z), c.shape[1], c.shape[0], C.byref(d), device, ptr(out)))
     return out
 
 
