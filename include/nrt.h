@@ -316,6 +316,33 @@ int nrt_denoise(const float* colour, const float* albedo, const float* normal, c
 int nrt_denoise_device(const nrt_scene* scene, const float* dev_colour, const float* dev_albedo,
                        const float* dev_normal, const float* dev_depth, uint32_t width, uint32_t rows,
                        const nrt_denoise_opts* dopts, int32_t device, float* dev_out, void* hip_stream);
+typedef struct {
+    uint32_t iterations; /* a-trous passes K, 1..5; 0 = 5.  Pass i has step 2^i */
+    float sigma_luminance, sigma_normal, sigma_depth; /* <= 0: the defaults 4, 0.3, 0.5 */
+} nrt_denoise_vg_opts;
+/* Variance-guided a-trous filter: the spatial filter of SVGF (Schied et al. 2017) with its spatial
+ * variance estimate (reference counterpart: none).  a, D_0, the steps, the taps and h as for
+ * nrt_denoise; lum(x) = 0.2126 x_r + 0.7152 x_g + 0.0722 x_b, l_i = lum(D_i),
+ *   g(p, q) = |N(p) - N(q)|^2 / sigma_normal^2 + (Z(p) - Z(q))^2 / sigma_depth^2,
+ * taps outside the image skipped in every sum.  Over q = p + (dx, dy), |dx|, |dy| <= 3, with
+ * w = exp(-g(p, q)) and d = l_0(q) - l_0(p):
+ *   Var_0(p) = max(0, sum w d^2 / sum w - (sum w d / sum w)^2)
+ * Pass i = 0 .. K-1, with g3 = (1/4, 1/2, 1/4) over the 3 x 3 pixels at distance 1 (not s):
+ *   sigma(p) = sqrt(sum g3[dx] g3[dy] Var_i(q) / sum g3[dx] g3[dy])
+ *   e(p, q) = |l_i(p) - l_i(q)| / (sigma_luminance sigma(p) + 1e-6) + g(p, q)
+ *   w = h[dx] h[dy] exp(-e),  D_{i+1}(p) = sum w D_i(q) / sum w,  Var_{i+1}(p) = sum w^2 Var_i(q) / (sum w)^2
+ * out = D_K a; out_variance (1 f32 per pixel, may be NULL) = Var_K, the variance of the demodulated
+ * luminance.  Buffers, overlap (out may be colour, for every K), dopts NULL, determinism, device and
+ * synchrony as nrt_denoise. */
+int nrt_denoise_vg(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
+                   uint32_t rows, const nrt_denoise_vg_opts* dopts, int32_t device, float* out, float* out_variance);
+/* Same over device memory, K + 1 launches enqueued on `hip_stream`, asynchronous (reference
+ * counterpart: none).  The scene owns the scratch (two colour-and-variance buffers and the packed
+ * guide records, 48 B per pixel, apart from nrt_denoise_device's), under nrt_denoise_device's rules. */
+int nrt_denoise_vg_device(const nrt_scene* scene, const float* dev_colour, const float* dev_albedo,
+                          const float* dev_normal, const float* dev_depth, uint32_t width, uint32_t rows,
+                          const nrt_denoise_vg_opts* dopts, int32_t device, float* dev_out, float* dev_out_variance,
+                          void* hip_stream);
 
 /* Number of rows selected by opts for an image of `height` rows. */
 uint32_t nrt_rows_selected(uint32_t height, const nrt_render_opts* opts);

@@ -29,8 +29,10 @@ struct nrt_scene {
     std::map<std::tuple<int, int, bool>, MultiRender*> multi;
     MultiRender* last_multi = nullptr;
     std::vector<DenoiseScratch*> denoise;  // the filter's scratch (nrt_denoise_device), index = HIP ordinal
+    std::vector<DenoiseScratch*> denoise_vg;  // the variance-guided filter's (nrt_denoise_vg_device)
     ~nrt_scene() {
         for (DenoiseScratch* d : denoise) gpu_denoise_scratch_free(d);
+        for (DenoiseScratch* d : denoise_vg) gpu_denoise_scratch_free(d);
         for (auto& kv : multi) gpu_multi_free(kv.second);  // (before the device scenes they render)
         for (DeviceScene* d : per_device) gpu_free_scene(d);
     }
@@ -700,16 +702,16 @@ namespace {
 
 struct DenoiseArgs {
     uint32_t iterations;
-    float sigma_color, sigma_normal, sigma_depth;
+    float sigma_color, sigma_normal, sigma_depth;  // (sigma_color: the variance-guided filter's sigma_luminance)
 };
 
 DenoiseArgs denoise_args(const void* c, const void* a, const void* n, const void* z, const void* out, uint32_t width,
-                         uint32_t rows, const nrt_denoise_opts* o) {
+                         uint32_t rows, const nrt_denoise_opts* o, float sigma_color_default = 0.6f) {
     if (!c || !a || !n || !z || !out) throw std::invalid_argument("null argument");
     // (the lattice grid of step 16 has rows / 8 + 16 workgroup rows: below HIP's 65 536)
     if (width == 0 || rows == 0 || width > (1u << 24) || rows > (1u << 18))
         throw std::invalid_argument("denoise: width in 1..2^24 and rows in 1..2^18");
-    DenoiseArgs d{5u, 0.6f, 0.3f, 0.5f};
+    DenoiseArgs d{5u, sigma_color_default, 0.3f, 0.5f};
     if (o) {
         if (o->iterations > 5) throw std::invalid_argument("denoise: iterations must be 1..5 (0 = 5)");
         if (o->iterations) d.iterations = o->iterations;
@@ -718,6 +720,13 @@ DenoiseArgs denoise_args(const void* c, const void* a, const void* n, const void
         if (o->sigma_depth > 0.0f) d.sigma_depth = o->sigma_depth;
     }
     return d;
+}
+
+DenoiseArgs denoise_vg_args(const void* c, const void* a, const void* n, const void* z, const void* out,
+                            uint32_t width, uint32_t rows, const nrt_denoise_vg_opts* o) {
+    nrt_denoise_opts d{};
+    if (o) d = nrt_denoise_opts{o->iterations, o->sigma_luminance, o->sigma_normal, o->sigma_depth};
+    return denoise_args(c, a, n, z, out, width, rows, o ? &d : nullptr, 4.0f);
 }
 
 int device_or_current(int32_t device) {
@@ -824,6 +833,61 @@ int nrt_denoise(const float* colour, const float* albedo, const float* normal, c
                         a.sigma_normal, a.sigma_depth, dout, nullptr);
             device_sync(dev);
             device_copy_to_host(out, dout, n * 3 * sizeof(float), dev);
+        } catch (...) {
+            gpu_denoise_scratch_free(scratch);
+            if (d) device_free(d, dev);
+            throw;
+        }
+        gpu_denoise_scratch_free(scratch);
+        device_free(d, dev);
+        return NRT_OK;
+    });
+}
+
+int nrt_denoise_vg_device(const nrt_scene* scene, const float* dev_colour, const float* dev_albedo,
+                          const float* dev_normal, const float* dev_depth, uint32_t width, uint32_t rows,
+                          const nrt_denoise_vg_opts* dopts, int32_t device, float* dev_out, float* dev_out_variance,
+                          void* hip_stream) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        if (!scene) throw std::invalid_argument("null argument");
+        const DenoiseArgs a = denoise_vg_args(dev_colour, dev_albedo, dev_normal, dev_depth, dev_out, width, rows, dopts);
+        const int dev = device_or_current(device);
+        nrt_scene* s = const_cast<nrt_scene*>(scene);
+        DenoiseScratch* scratch = nullptr;
+        {
+            std::lock_guard<std::mutex> lock(s->mu);
+            if ((int)s->denoise_vg.size() <= dev) s->denoise_vg.resize((size_t)dev + 1, nullptr);
+            DenoiseScratch*& slot = s->denoise_vg[(size_t)dev];
+            DenoiseScratch* have = slot;
+            slot = nullptr;  // (gpu_denoise_scratch frees `have` before it can throw)
+            scratch = slot = gpu_denoise_scratch(have, (size_t)width * rows, dev, 16);
+        }
+        gpu_denoise_vg(scratch, dev_colour, dev_albedo, dev_normal, dev_depth, width, rows, a.iterations, a.sigma_color,
+                       a.sigma_normal, a.sigma_depth, dev_out, dev_out_variance, hip_stream);
+        return NRT_OK;
+    });
+}
+
+int nrt_denoise_vg(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
+                   uint32_t rows, const nrt_denoise_vg_opts* dopts, int32_t device, float* out, float* out_variance) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        const DenoiseArgs a = denoise_vg_args(colour, albedo, normal, depth, out, width, rows, dopts);
+        const int dev = device_or_current(device);
+        const size_t n = (size_t)width * rows;
+        float* d = nullptr;  // colour, filtered in place | albedo | normal | depth | variance
+        DenoiseScratch* scratch = nullptr;
+        try {
+            d = (float*)device_alloc(n * 11 * sizeof(float), dev);
+            scratch = gpu_denoise_scratch(nullptr, n, dev, 16);
+            device_copy_from_host(d, colour, n * 3 * sizeof(float), dev);
+            device_copy_from_host(d + 3 * n, albedo, n * 3 * sizeof(float), dev);
+            device_copy_from_host(d + 6 * n, normal, n * 3 * sizeof(float), dev);
+            device_copy_from_host(d + 9 * n, depth, n * sizeof(float), dev);
+            gpu_denoise_vg(scratch, d, d + 3 * n, d + 6 * n, d + 9 * n, width, rows, a.iterations, a.sigma_color,
+                           a.sigma_normal, a.sigma_depth, d, out_variance ? d + 10 * n : nullptr, nullptr);
+            device_sync(dev);
+            device_copy_to_host(out, d, n * 3 * sizeof(float), dev);
+            if (out_variance) device_copy_to_host(out_variance, d + 10 * n, n * sizeof(float), dev);
         } catch (...) {
             gpu_denoise_scratch_free(scratch);
             if (d) device_free(d, dev);

@@ -4,7 +4,8 @@
 // (render.rs:57-62), gamma 0.5 + to_rgb8 + write (render.rs:74-102).
 // Extra flags: --precision {f64,f32}, --rng {chacha8,philox}, --gpus N, --legacy-schema (also
 // load the index schema of scenes/triangles.toml, NRT_LOAD_LEGACY_SCHEMA), --denoise[=K] (the
-// a-trous filter over the frame and its first-hit feature buffers, K = 1..5 passes, default 5).
+// a-trous filter over the frame and its first-hit feature buffers, K = 1..5 passes, default 5),
+// --denoise-vg[=K] (the variance-guided a-trous filter instead; not with --denoise).
 // Output formats: .png (stored deflate), .ppm, .pfm (linear f32).
 //
 // `nrt-cli convert-stl <STL> [-o FILE] [-f] [-F toml|json]` — the reference's
@@ -218,7 +219,8 @@ void usage() {
             "       [--background-color X,Y,Z] [--look-at X,Y,Z] [--look-from X,Y,Z] [--view-up X,Y,Z]\n"
             "       [--focal-length F] [--field-of-view DEG] [--defocus-angle DEG] [--focus-distance D]\n"
             "       [--samples-per-pixel N] [--ray-max-bounces N] [-v]\n"
-            "       [--precision f64|f32] [--rng chacha8|philox] [--gpus N] [--legacy-schema] [--denoise[=K]]\n");
+            "       [--precision f64|f32] [--rng chacha8|philox] [--gpus N] [--legacy-schema]\n"
+            "       [--denoise[=K] | --denoise-vg[=K]]\n");
     exit(2);
 }
 
@@ -232,7 +234,8 @@ int main(int argc, char** argv) {
     uint32_t load_flags = 0;
     float gamma = 0.5f;
     int gpus = 1;
-    uint32_t denoise = 0;  // a-trous passes (0: no filter)
+    uint32_t denoise = 0;     // a-trous passes (0: no filter)
+    uint32_t denoise_vg = 0;  // variance-guided a-trous passes (0: no filter)
     nrt_camera_config cc{};
     nrt_render_opts opts{};
     opts.device = -1;
@@ -278,11 +281,17 @@ int main(int argc, char** argv) {
             denoise = (uint32_t)atoi(a.c_str() + 10);
             if (denoise < 1 || denoise > 5) die("--denoise=K: K must be 1..5");
         }
+        else if (a == "--denoise-vg") denoise_vg = 5;
+        else if (a.rfind("--denoise-vg=", 0) == 0) {
+            denoise_vg = (uint32_t)atoi(a.c_str() + 13);
+            if (denoise_vg < 1 || denoise_vg > 5) die("--denoise-vg=K: K must be 1..5");
+        }
         else if (a.rfind("--", 0) == 0) kv.emplace_back(a, val());
         else if (scene.empty()) scene = a;
         else usage();
     }
     if (scene.empty()) usage();
+    if (denoise && denoise_vg) die("--denoise and --denoise-vg are mutually exclusive");
     for (auto& kvp : kv) {
         const std::string& k = kvp.first;
         const std::string& v = kvp.second;
@@ -383,7 +392,7 @@ int main(int argc, char** argv) {
         die(nrt_last_error());
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (denoise) {  // before the output stage: feature buffers on the first device, the frame filtered in place
+    if (denoise || denoise_vg) {  // before the output stage: feature buffers on the first device, the frame filtered in place
         const auto td = std::chrono::steady_clock::now();
         const size_t n = (size_t)W * H;
         std::vector<float> albedo(n * 3), normal(n * 3), depth(n);
@@ -392,11 +401,17 @@ int main(int argc, char** argv) {
         ao.device = gpus > 1 ? dev_of(0) : opts.device;
         nrt_denoise_opts dopts{};
         dopts.iterations = denoise;
+        nrt_denoise_vg_opts vopts{};
+        vopts.iterations = denoise_vg;
         if (nrt_render_aov(sc, &cam, &ao, albedo.data(), normal.data(), depth.data(), n) != NRT_OK ||
-            nrt_denoise(img.data(), albedo.data(), normal.data(), depth.data(), W, H, &dopts, ao.device, img.data()) != NRT_OK)
+            (denoise_vg ? nrt_denoise_vg(img.data(), albedo.data(), normal.data(), depth.data(), W, H, &vopts, ao.device,
+                                         img.data(), nullptr)
+                        : nrt_denoise(img.data(), albedo.data(), normal.data(), depth.data(), W, H, &dopts, ao.device,
+                                      img.data())) != NRT_OK)
             die(nrt_last_error());
         if (verbose)
-            fprintf(stderr, " Denoising (%u passes) - Done in %.3f secs\n", denoise,
+            fprintf(stderr, " Denoising (%u%s passes) - Done in %.3f secs\n", denoise + denoise_vg,
+                    denoise_vg ? " variance-guided" : "",
                     std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count());
     }
     if (verbose) {

@@ -52,14 +52,20 @@ void gpu_launch_aov(const DeviceScene* ds, const RenderParams& p, uint32_t trace
                     float* depth, void* stream);
 // A-trous filter (denoise.hip).  The scratch (two colour buffers and the packed guide records) holds
 // `pixels` pixels on `device`; gpu_denoise_scratch returns `have` when it is large enough, else frees it
-// and allocates anew (have may be null).
+// and allocates anew (have may be null).  rec_bytes: a colour buffer's bytes per pixel, 12 for gpu_denoise,
+// 16 (colour and variance) for gpu_denoise_vg.
 struct DenoiseScratch;
-DenoiseScratch* gpu_denoise_scratch(DenoiseScratch* have, size_t pixels, int device);  // throws
+DenoiseScratch* gpu_denoise_scratch(DenoiseScratch* have, size_t pixels, int device, size_t rec_bytes = 12);  // throws
 void gpu_denoise_scratch_free(DenoiseScratch* s);
 // Enqueue the `iterations` passes on `stream` (device pointers; out may be colour); sigmas > 0.
 void gpu_denoise(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
                  uint32_t width, uint32_t rows, uint32_t iterations, float sigma_color, float sigma_normal,
                  float sigma_depth, float* out, void* stream);
+// Variance-guided filter: the moments kernel and the `iterations` passes (scratch with rec_bytes 16; out may
+// be colour; out_variance may be null).
+void gpu_denoise_vg(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
+                    uint32_t width, uint32_t rows, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                    float sigma_depth, float* out, float* out_variance, void* stream);
 // First `count` draws of `lanes` consecutive streams starting at stream0 (tests).
 struct JitCounts {
     uint64_t compiled, launches, failed, compile_ns, disk_hits, load_retries;

@@ -78,6 +78,11 @@ class _DenoiseOpts(C.Structure):
                 ("sigma_depth", C.c_float)]
 
 
+class _DenoiseVgOpts(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64)
 
 # Every symbol include/nrt.h declares, with its ctypes signature.
@@ -135,6 +140,10 @@ SIGNATURES = {
                               C.POINTER(C.c_float)]),
     "nrt_denoise_device": (C.c_int, [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseOpts), C.c_int32,
                                      C.c_void_p, C.c_void_p]),
+    "nrt_denoise_vg": (C.c_int, [C.POINTER(C.c_float)] * 4 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseVgOpts),
+                                 C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nrt_denoise_vg_device": (C.c_int, [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseVgOpts), C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrt_rows_selected": (C.c_uint32, [C.c_uint32, C.POINTER(_RenderOpts)]),
     "nrt_scene_upload": (C.c_int, [C.c_void_p, C.c_int32]),
     "nrt_scene_stats_get": (C.c_int, [C.c_void_p, C.POINTER(_SceneStats)]),
@@ -423,15 +432,20 @@ class Scene:
         """Camera::render -> Rgb32FImage as float32 array (rows, W, 3).  gpus = N >= 1: the whole frame
         over devices device .. device+N-1 (device -1: 0), one RCCL gather (nrt_render_opts.gpus).
         denoise = True (or the number of passes, 1..5): the frame, then its feature buffers
-        (render_aov), then the a-trous filter (nrt.denoise) over both; whole frames on one device."""
+        (render_aov), then the a-trous filter (nrt.denoise) over both; whole frames on one device.
+        denoise = "variance": the same chain with the variance-guided filter (nrt.denoise_vg)."""
         cam = camera or self.camera
         if cam is None:
             raise ValueError("no camera")
+        if isinstance(denoise, str) and denoise != "variance":
+            raise ValueError(f"denoise must be False, True, 1..5 or 'variance', not {denoise!r}")
         if denoise:
             if row_stride > 1 or row_offset:
                 raise ValueError("denoise filters whole frames: row_offset 0 and row_stride 1")
             frame = self.render(cam, precision, rng, device, progress=progress, trace=trace, gpus=gpus)
             aov = self.render_aov(cam, trace=trace, device=device)
+            if denoise == "variance":
+                return denoise_vg(frame, device=device, out=frame, **aov)
             return globals()["denoise"](frame, iterations=5 if denoise is True else int(denoise), device=device,
                                         out=frame, **aov)
         o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus)
@@ -478,6 +492,17 @@ class Scene:
         _check(lib().nrt_denoise_device(self._h, C.c_void_p(colour_ptr), C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr),
                                         C.c_void_p(depth_ptr), width, rows, C.byref(d), device, C.c_void_p(out_ptr),
                                         C.c_void_p(stream)))
+
+    def denoise_vg_device(self, colour_ptr: int, albedo_ptr: int, normal_ptr: int, depth_ptr: int, width: int,
+                          rows: int, out_ptr: int, variance_ptr: int = 0, iterations: int = 5,
+                          sigma_luminance: float = 4.0, sigma_normal: float = 0.3, sigma_depth: float = 0.5,
+                          device: int = -1, stream: int = 0) -> None:
+        """Enqueue the variance-guided filter over device memory (nrt_denoise_vg_device; the scene owns the
+        scratch); out_ptr may be colour_ptr, variance_ptr may be 0."""
+        d = _DenoiseVgOpts(iterations, sigma_luminance, sigma_normal, sigma_depth)
+        _check(lib().nrt_denoise_vg_device(self._h, C.c_void_p(colour_ptr), C.c_void_p(albedo_ptr),
+                                           C.c_void_p(normal_ptr), C.c_void_p(depth_ptr), width, rows, C.byref(d),
+                                           device, C.c_void_p(out_ptr), C.c_void_p(variance_ptr), C.c_void_p(stream)))
 
     def phase_profile(self, camera: Optional[Camera] = None, precision: str = "f32", rng: str = "philox",
                       device: int = -1, trace: str = "auto") -> dict:
@@ -659,6 +684,33 @@ def denoise(colour: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth: n
     d = _DenoiseOpts(iterations, sigma_color, sigma_normal, sigma_depth)
     ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
     _check(lib().nrt_denoise(ptr(c), ptr(a), ptr(n), ptr(z), c.shape[1], c.shape[0], C.byref(d), device, ptr(out)))
+    return out
+
+
+def denoise_vg(colour: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth: np.ndarray, iterations: int = 5,
+               sigma_luminance: float = 4.0, sigma_normal: float = 0.3, sigma_depth: float = 0.5, device: int = -1,
+               out: Optional[np.ndarray] = None, variance_out: Optional[np.ndarray] = None) -> np.ndarray:
+    """Variance-guided a-trous filter (nrt_denoise_vg; SVGF's spatial filter with its 7x7 variance estimate) of a
+    (rows, W, 3) frame with its feature buffers, as `denoise`; `variance_out`, a (rows, W) float32 array, receives
+    the filtered variance of the demodulated luminance."""
+    def f32(a):
+        return a if a.dtype == np.float32 and a.flags.c_contiguous else np.ascontiguousarray(a, dtype=np.float32)
+
+    c, a, n, z = f32(colour), f32(albedo), f32(normal), f32(depth)
+    if c.ndim != 3 or c.shape[2] != 3 or a.shape != c.shape or n.shape != c.shape or z.shape != c.shape[:2]:
+        raise NrtError(-1, f"denoise_vg: colour {c.shape}, albedo {a.shape}, normal {n.shape}, depth {z.shape} do "
+                           "not describe one (rows, W, 3) frame")
+    if out is None:
+        out = np.empty_like(c)
+    elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != c.shape:
+        raise NrtError(-1, "denoise_vg: out must be a contiguous float32 array of the frame's shape")
+    v = variance_out
+    if v is not None and (v.dtype != np.float32 or not v.flags.c_contiguous or v.shape != c.shape[:2]):
+        raise NrtError(-1, "denoise_vg: variance_out must be a contiguous float32 array of shape (rows, W)")
+    d = _DenoiseVgOpts(iterations, sigma_luminance, sigma_normal, sigma_depth)
+    ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+    _check(lib().nrt_denoise_vg(ptr(c), ptr(a), ptr(n), ptr(z), c.shape[1], c.shape[0], C.byref(d), device, ptr(out),
+                                ptr(v) if v is not None else None))
     return out
 
 

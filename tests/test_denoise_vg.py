@@ -1,0 +1,136 @@
+"""Variance-guided a-trous filter (nrt_denoise_vg): the filter against its definition (include/nrt.h)
+restated in numpy f64, the plumbing from Scene.render(denoise="variance") down to the device entry point,
+and the argument errors.
+
+Tolerances: colour max|out - ref| <= 5e-5 max|ref|, the bound of test_denoise.py (an f32 exponent argument
+on a convex weighted mean, five passes); variance <= 5e-5 max Var_0 (a sum of w^2 Var / (sum w)^2 with
+w <= sum w never exceeds max Var_0).  The same formulas in numpy f32 differ from f64 by 4.6e-7 and 1.9e-7
+on these scales."""
+import numpy as np
+import pytest
+
+import nrt
+from helpers import in_golden
+
+H5 = (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16)
+G3 = (1 / 4, 1 / 2, 1 / 4)
+
+
+def taps(H, W, r, s):
+    """(dx, dy, P, Q) of the taps q = p + s (dx, dy), |dx|, |dy| <= r: P the pixels whose tap lies in the image."""
+    for dy in range(-r, r + 1):
+        for dx in range(-r, r + 1):
+            y0, y1, x0, x1 = max(0, -dy * s), min(H, H - dy * s), max(0, -dx * s), min(W, W - dx * s)
+            if y0 < y1 and x0 < x1:
+                yield dx, dy, (slice(y0, y1), slice(x0, x1)), (slice(y0 + dy * s, y1 + dy * s), slice(x0 + dx * s, x1 + dx * s))
+
+
+def vg_f64(C, A, N, Z, K, sl=4.0, sn=0.3, sz=0.5):
+    C, A, N, Z = (x.astype(np.float64) for x in (C, A, N, Z))
+    H, W, _ = C.shape
+    a = np.maximum(A, 1e-3)
+    D = C / a
+    lum = lambda x: 0.2126 * x[..., 0] + 0.7152 * x[..., 1] + 0.0722 * x[..., 2]  # noqa: E731
+    g = lambda P, Q: ((N[P] - N[Q]) ** 2).sum(-1) / sn ** 2 + (Z[P] - Z[Q]) ** 2 / sz ** 2  # noqa: E731
+    l, sw, s1, s2 = lum(D), np.zeros((H, W)), np.zeros((H, W)), np.zeros((H, W))
+    for dx, dy, P, Q in taps(H, W, 3, 1):
+        w, d = np.exp(-g(P, Q)), l[Q] - l[P]
+        sw[P] += w
+        s1[P] += w * d
+        s2[P] += w * d * d
+    var0 = var = np.maximum(0.0, s2 / sw - (s1 / sw) ** 2)
+    for i in range(K):
+        num, den = np.zeros((H, W)), np.zeros((H, W))
+        for dx, dy, P, Q in taps(H, W, 1, 1):
+            num[P] += G3[dx + 1] * G3[dy + 1] * var[Q]
+            den[P] += G3[dx + 1] * G3[dy + 1]
+        sigma, l = np.sqrt(num / den), lum(D)
+        nD, nv, sw = np.zeros_like(D), np.zeros((H, W)), np.zeros((H, W))
+        for dx, dy, P, Q in taps(H, W, 2, 1 << i):
+            w = H5[dx + 2] * H5[dy + 2] * np.exp(-(np.abs(l[P] - l[Q]) / (sl * sigma[P] + 1e-6) + g(P, Q)))
+            nD[P] += w[..., None] * D[Q]
+            nv[P] += w * w * var[Q]
+            sw[P] += w
+        D, var = nD / sw[..., None], nv / sw ** 2
+    return D * a, var, var0
+
+
+def synthetic(H, W):
+    """test_denoise.py's frame: two regions split by a slanted line (normals, depth ramps), a 3-row miss
+    band, a 4-pixel checker albedo, colour = base * albedo * (1 + 0.5 gauss); float32."""
+    rng = np.random.default_rng(1000 * H + W)
+    ys, xs = np.mgrid[0:H, 0:W]
+    left = xs < W * 0.45 + ys * 0.2
+    N = np.where(left[..., None], [0, 0, 1.0], [0.6, 0, 0.8])
+    Z = np.where(left, 2.0 + 0.01 * xs, 3.5 + 0.02 * ys)
+    N[:3], Z[:3] = 0, 0
+    A = np.where(((xs // 4 + ys // 4) % 2)[..., None] == 0, [0.8, 0.3, 0.2], [0.2, 0.7, 0.9])
+    A[:3] = [0.1, 0.2, 0.3]
+    C = np.abs(np.where(left[..., None], 0.7, 0.25) * A * (1 + 0.5 * rng.standard_normal((H, W, 3))))
+    return tuple(np.ascontiguousarray(x, dtype=np.float32) for x in (C, A, N, Z))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 3, 5])
+@pytest.mark.parametrize("shape", [(6, 9), (29, 37), (45, 70)])
+def test_filter_matches_f64_definition(shape, K):
+    """Measured on an MI355X: see DESIGN.md (the variance-guided filter's accuracy item)."""
+    C, A, N, Z = synthetic(*shape)
+    ref, ref_var, var0 = vg_f64(C, A, N, Z, K)
+    var = np.empty(shape, np.float32)
+    out = nrt.denoise_vg(C, A, N, Z, iterations=K, variance_out=var)
+    err, scale = np.abs(out - ref).max(), np.abs(ref).max()
+    verr, vscale = np.abs(var - ref_var).max(), var0.max()
+    print(f"vg a-trous {shape} K={K}: max|out - ref| = {err:.3e} = {err / scale:.3e} max|ref|; "
+          f"max|var - ref| = {verr:.3e} = {verr / vscale:.3e} max Var_0")
+    assert err <= 5e-5 * scale
+    assert verr <= 5e-5 * vscale
+    assert np.array_equal(nrt.denoise_vg(C, A, N, Z, iterations=K), out)  # run to run, and without a variance buffer
+    inplace = C.copy()
+    assert nrt.denoise_vg(inplace, A, N, Z, iterations=K, out=inplace) is inplace
+    assert np.array_equal(inplace, out)
+    if K == 5 and shape == (45, 70):
+        assert not np.array_equal(out, nrt.denoise(C, A, N, Z))  # not the fixed-sigma filter
+
+
+@pytest.mark.gpu
+def test_plumbing_render_variance_and_device_entry_point():
+    torch = pytest.importorskip("torch")  # nrt.lib() already imported it first: one HIP runtime
+    W = H = 48
+    with in_golden():
+        s = nrt.Scene.load("scenes/cornell-box-scene.json", nrt.CameraConfig(width=W, height=H, samples_per_pixel=4))
+    frame = s.render(precision="f32", rng="philox")
+    aov = s.render_aov()
+    var = np.empty((H, W), np.float32)
+    want = nrt.denoise_vg(frame, variance_out=var, **aov)
+    assert np.array_equal(s.render(precision="f32", rng="philox", denoise="variance"), want)
+    assert np.array_equal(s.render(precision="f32", rng="philox", denoise=True), nrt.denoise(frame, **aov))
+    dev = {k: torch.from_numpy(v).to("cuda:0") for k, v in aov.items()}
+    dvar = torch.empty((H, W), dtype=torch.float32, device="cuda:0")
+    st = torch.cuda.current_stream(0).cuda_stream
+    for _ in range(2):  # scene-owned scratch, in place, twice: the host call's bits
+        col = torch.from_numpy(frame).to("cuda:0")
+        s.denoise_vg_device(col.data_ptr(), dev["albedo"].data_ptr(), dev["normal"].data_ptr(), dev["depth"].data_ptr(),
+                            W, H, col.data_ptr(), dvar.data_ptr(), device=0, stream=st)
+        torch.cuda.synchronize(0)
+        assert np.array_equal(col.cpu().numpy(), want)
+        assert np.array_equal(dvar.cpu().numpy(), var)
+
+
+def test_argument_errors_and_missing_device():
+    c = np.ones((4, 5, 3), np.float32)
+    if nrt.device_count() == 0:
+        with pytest.raises(nrt.NrtError) as ei:
+            nrt.denoise_vg(c, c, c, c[..., 0])
+        assert ei.value.code == -3
+    for bad in (lambda: nrt.denoise_vg(c, c, c, c[..., 0], iterations=6),
+                lambda: nrt.denoise_vg(c, c, c[:3], c[..., 0]),
+                lambda: nrt.denoise_vg(c, c, c, c[:, :4, 0]),
+                lambda: nrt.denoise_vg(c, c, c, c[..., 0], variance_out=np.empty((4, 4), np.float32))):
+        with pytest.raises(nrt.NrtError) as ei:
+            bad()
+        assert ei.value.code == -1
+    b = nrt.Builder()
+    scene = b.finish(b.bvh([b.sphere((0, 0, 0), 1.0, b.lambertian(b.solid((1, 1, 1))))]))
+    with pytest.raises(ValueError):
+        scene.render(nrt.CameraBuilder(width=4, height=4, samples_per_pixel=1).build(), denoise="bogus")
