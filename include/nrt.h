@@ -343,6 +343,63 @@ int nrt_denoise_vg_device(const nrt_scene* scene, const float* dev_colour, const
                           const float* dev_normal, const float* dev_depth, uint32_t width, uint32_t rows,
                           const nrt_denoise_vg_opts* dopts, int32_t device, float* dev_out, float* dev_out_variance,
                           void* hip_stream);
+/* ---- temporal accumulation in front of the variance-guided filter: SVGF (Schied et al. 2017) whole
+ *      (reference counterpart: none).  The scene is static between frames, so reprojection is a
+ *      function of the two cameras and the depth buffer alone. */
+typedef struct nrt_history nrt_history;
+typedef struct {
+    uint32_t iterations; /* a-trous passes K, 2..5; 0 = 5 (the history takes the first pass's output) */
+    float sigma_luminance, sigma_normal, sigma_depth; /* <= 0: the defaults 4, 0.3, 0.5 */
+    float alpha_min; /* <= 0: 0.2 */
+    float tau_z;     /* <= 0: 0.1 */
+    float tau_n;     /* <= 0: 0.9 */
+} nrt_denoise_temporal_opts;
+/* A history of `width` x `rows` frames on `device` (-1 = the device current at the first frame).  It
+ * owns every buffer, state and work: 112 B per pixel, allocated by the first frame (NULL: a zero size). */
+nrt_history* nrt_history_new(uint32_t width, uint32_t rows, int32_t device);
+void nrt_history_free(nrt_history* history);
+/* The next frame's history is invalid at every pixel. */
+int nrt_history_reset(nrt_history* history);
+/* a, D = colour / a, lum, g(p, q), h, the steps, the passes and Var_0 as for nrt_denoise_vg.  The
+ * history holds, of the previous frame ('): its camera, its guide records N', Z', its colour history H'
+ * (rgb), its luminance moments m1', m2' and an integer history length n'.  Frame k with `camera`, at
+ * pixel p = (x, y), l = lum(D(p)):
+ *   d = top_left + x pixel_delta_u + y pixel_delta_v - look_from,  P = look_from + Z(p) d / |d|,
+ *   r = P - look_from',  (A, B, Cc) = M'^-1 r with the columns of M' pixel_delta_u', pixel_delta_v',
+ *   top_left' - look_from';  u = A / Cc, v = B / Cc, z' = |r|.
+ * The host inverts M' in f64 (singular: NRT_E_INVALID) and hands the kernel f32 constants of the
+ * equivalent form, with k = Z(p) / |d| and M's columns those of this camera,
+ *   (A, B, Cc) = k (x, y, 1) + k M'^-1 (M - M') (x, y, 1) + M'^-1 (look_from - look_from'),
+ * which makes u = x, v = y exact for equal cameras.  Taps q = (floor(u) + i, floor(v) + j), i, j in
+ * {0, 1}, with the bilinear weights b_q of (u, v); a tap is valid when it lies in the image, Z'(q) > 0,
+ * |Z'(q) - z'| <= tau_z z' and N'(q) . N(p) >= tau_n; sb = the sum of b_q over the valid taps.  The
+ * history of p is valid when the history object holds a frame, Z(p) > 0, Cc > 0 and sb >= 0.01:
+ *   Hh, M1, M2 = sum b_q (H', m1', m2')(q) / sb over the valid taps,
+ *   n = min(1 + min over the valid taps of n'(q), 255),  alpha = max(alpha_min, 1 / n),
+ *   I(p) = Hh + alpha (D(p) - Hh),  m1 = M1 + alpha (l - M1),  m2 = M2 + alpha (l^2 - M2);
+ * otherwise I = D, m1 = l, m2 = l^2, n = 1.  The variance:
+ *   V(p) = max(0, m2 - m1^2) when n >= 4, else Var_0(p) / n
+ * (the frame's variance over the frames averaged is the variance of their mean; with alpha >= 1 / n the
+ * blend is that mean for n < 4).  Then nrt_denoise_vg's K passes from (I, V) in place of (D_0, Var_0):
+ * out = D_K a, out_variance = Var_K.  The new history: H = D_1.rgb (the first pass's output, SVGF's
+ * feedback: K >= 2), m1, m2, n as above, N, Z and the camera of this frame.  The history length is an
+ * integer minimum, not a bilinear mix, so the n >= 4 branch never sits on a rounding edge.
+ * Host buffers as nrt_denoise_vg's (out may be colour; out_variance, 1 f32 per pixel, may be NULL and
+ * overlaps nothing; no other overlap), synchronous.  NRT_E_INVALID: a camera whose size is not the
+ * history's, K = 1 or K > 5, an overlap; NRT_E_DEVICE: no usable device.  No atomics, every sum by one
+ * lane in one order: a pure function of the frames so far, the same bits from run to run. */
+int nrt_denoise_temporal(nrt_history* history, const nrt_camera* camera, const float* colour, const float* albedo,
+                         const float* normal, const float* depth, const nrt_denoise_temporal_opts* opts, float* out,
+                         float* out_variance);
+/* Same over device memory on the history's device, K + 1 launches enqueued on `hip_stream`,
+ * asynchronous: calls on one history must be ordered by their streams. */
+int nrt_denoise_temporal_device(nrt_history* history, const nrt_camera* camera, const float* dev_colour,
+                                const float* dev_albedo, const float* dev_normal, const float* dev_depth,
+                                const nrt_denoise_temporal_opts* opts, float* dev_out, float* dev_out_variance,
+                                void* hip_stream);
+/* The last frame's m1, m2 (moments: 2 f32 per pixel) and n (length: 1 f32 per pixel) to host memory,
+ * after the device has finished; either pointer may be NULL.  NRT_E_INVALID before the first frame. */
+int nrt_history_read(nrt_history* history, float* moments, float* length);
 
 /* Number of rows selected by opts for an image of `height` rows. */
 uint32_t nrt_rows_selected(uint32_t height, const nrt_render_opts* opts);

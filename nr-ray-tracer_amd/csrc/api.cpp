@@ -899,6 +899,135 @@ int nrt_denoise_vg(const float* colour, const float* albedo, const float* normal
     });
 }
 
+// ---- temporal accumulation (denoise.hip, second half)
+struct nrt_history {
+    History* h = nullptr;
+    uint32_t width = 0, rows = 0;
+    int32_t device = -1;  // as asked for; the first frame resolves -1
+    ~nrt_history() { gpu_history_free(h); }
+};
+
+namespace {
+
+struct TemporalArgs {
+    DenoiseArgs d;
+    float alpha_min, tau_z, tau_n;
+    TemporalCamera cam;
+};
+
+bool overlap(const float* a, size_t na, const float* b, size_t nb) { return a && b && a < b + nb && b < a + na; }
+
+// Every check that needs no device, in one place for the two entry points.
+TemporalArgs temporal_args(const nrt_history* h, const nrt_camera* camera, const float* c, const float* a,
+                           const float* n, const float* z, const nrt_denoise_temporal_opts* o, const float* out,
+                           const float* var) {
+    if (!h || !camera) throw std::invalid_argument("null argument");
+    nrt_denoise_vg_opts v{};
+    if (o) v = nrt_denoise_vg_opts{o->iterations, o->sigma_luminance, o->sigma_normal, o->sigma_depth};
+    TemporalArgs t{denoise_vg_args(c, a, n, z, out, h->width, h->rows, o ? &v : nullptr), 0.2f, 0.1f, 0.9f, {}};
+    if (t.d.iterations < 2) throw std::invalid_argument("denoise_temporal: iterations must be 2..5 (0 = 5)");
+    if (camera->width != h->width || camera->height != h->rows)
+        throw std::invalid_argument("denoise_temporal: the camera's size is not the history's");
+    const size_t px = (size_t)h->width * h->rows;
+    const float* in[4] = {c, a, n, z};
+    const size_t len[4] = {3 * px, 3 * px, 3 * px, px};
+    for (int i = 0; i < 4; ++i) {
+        if ((overlap(out, 3 * px, in[i], len[i]) && !(i == 0 && out == c)) || overlap(var, px, in[i], len[i]))
+            throw std::invalid_argument("denoise_temporal: out may be colour; no other overlap");
+    }
+    if (overlap(var, px, out, 3 * px)) throw std::invalid_argument("denoise_temporal: out_variance overlaps out");
+    if (o) {
+        if (o->alpha_min > 0.0f) t.alpha_min = o->alpha_min;
+        if (o->tau_z > 0.0f) t.tau_z = o->tau_z;
+        if (o->tau_n > 0.0f) t.tau_n = o->tau_n;
+    }
+    for (int i = 0; i < 3; ++i) {
+        t.cam.look_from[i] = camera->look_from[i];
+        t.cam.du[i] = camera->pixel_delta_u[i];
+        t.cam.dv[i] = camera->pixel_delta_v[i];
+        t.cam.top_left[i] = camera->top_left[i];
+    }
+    return t;
+}
+
+int history_device(const nrt_history* h) {
+    const int have = gpu_history_device(h->h);
+    return have >= 0 ? have : device_or_current(h->device);
+}
+
+void temporal_run(nrt_history* h, const TemporalArgs& t, int dev, const float* c, const float* a, const float* n,
+                  const float* z, float* out, float* var, void* stream) {
+    gpu_denoise_temporal(h->h, dev, t.cam, c, a, n, z, t.d.iterations, t.d.sigma_color, t.d.sigma_normal,
+                         t.d.sigma_depth, t.alpha_min, t.tau_z, t.tau_n, out, var, stream);
+}
+
+}  // namespace
+
+nrt_history* nrt_history_new(uint32_t width, uint32_t rows, int32_t device) {
+    nrt_history* h = nullptr;
+    guarded(NRT_E_INVALID, [&]() {
+        if (width == 0 || rows == 0 || width > (1u << 24) || rows > (1u << 18))
+            throw std::invalid_argument("history: width in 1..2^24 and rows in 1..2^18");
+        auto p = std::make_unique<nrt_history>();
+        p->h = gpu_history_new(width, rows);
+        p->width = width, p->rows = rows, p->device = device;
+        h = p.release();
+        return NRT_OK;
+    });
+    return h;
+}
+
+void nrt_history_free(nrt_history* history) { delete history; }
+
+int nrt_history_reset(nrt_history* history) {
+    return guarded(NRT_E_INVALID, [&]() {
+        if (!history) throw std::invalid_argument("null argument");
+        gpu_history_reset(history->h);
+        return NRT_OK;
+    });
+}
+
+int nrt_denoise_temporal_device(nrt_history* history, const nrt_camera* camera, const float* dev_colour,
+                                const float* dev_albedo, const float* dev_normal, const float* dev_depth,
+                                const nrt_denoise_temporal_opts* opts, float* dev_out, float* dev_out_variance,
+                                void* hip_stream) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        const TemporalArgs t = temporal_args(history, camera, dev_colour, dev_albedo, dev_normal, dev_depth, opts,
+                                             dev_out, dev_out_variance);
+        temporal_run(history, t, history_device(history), dev_colour, dev_albedo, dev_normal, dev_depth, dev_out,
+                     dev_out_variance, hip_stream);
+        return NRT_OK;
+    });
+}
+
+int nrt_denoise_temporal(nrt_history* history, const nrt_camera* camera, const float* colour, const float* albedo,
+                         const float* normal, const float* depth, const nrt_denoise_temporal_opts* opts, float* out,
+                         float* out_variance) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        const TemporalArgs t = temporal_args(history, camera, colour, albedo, normal, depth, opts, out, out_variance);
+        const int dev = history_device(history);
+        const size_t n = (size_t)history->width * history->rows;
+        float* d = gpu_history_io(history->h, dev);  // colour, filtered in place | albedo | normal | depth | variance
+        device_copy_from_host(d, colour, n * 3 * sizeof(float), dev);
+        device_copy_from_host(d + 3 * n, albedo, n * 3 * sizeof(float), dev);
+        device_copy_from_host(d + 6 * n, normal, n * 3 * sizeof(float), dev);
+        device_copy_from_host(d + 9 * n, depth, n * sizeof(float), dev);
+        temporal_run(history, t, dev, d, d + 3 * n, d + 6 * n, d + 9 * n, d, out_variance ? d + 10 * n : nullptr, nullptr);
+        device_sync(dev);
+        device_copy_to_host(out, d, n * 3 * sizeof(float), dev);
+        if (out_variance) device_copy_to_host(out_variance, d + 10 * n, n * sizeof(float), dev);
+        return NRT_OK;
+    });
+}
+
+int nrt_history_read(nrt_history* history, float* moments, float* length) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        if (!history) throw std::invalid_argument("null argument");
+        gpu_history_read(history->h, moments, length);
+        return NRT_OK;
+    });
+}
+
 int nrt_render_prepare(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts) {
     return guarded(NRT_E_DEVICE, [&]() {
         if (!scene || !camera) throw std::invalid_argument("null argument");

@@ -12,10 +12,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "gpu.hpp"
 
@@ -280,12 +282,9 @@ __device__ __forceinline__ float lum(float r, float g, float b) {
 // (4 B + 16 B, 10.6 KB).  Consecutive lanes read consecutive words / records at every tap, so neither
 // array has a bank conflict.  Each lane sums its 49 taps in one fixed order; the luminance is shifted
 // by the centre's, so the two moments stay of the noise's size and their difference does not cancel.
-__global__ void __launch_bounds__(THREADS) vg_moments_kernel(const VgParams p) {
-    __shared__ float4 sg[VPIX];
-    __shared__ float sl[VPIX];
+// (The two halves below are shared with temporal_kernel.)
+__device__ __forceinline__ void vg_stage(const VgParams& p, float4* sg, float* sl, int tx0, int ty0, int tid) {
     const int W = (int)p.width, H = (int)p.height;
-    const int tx0 = (int)blockIdx.x * TW, ty0 = (int)blockIdx.y * TH;
-    const int tid = (int)threadIdx.x;
     for (int q = tid; q < VPIX; q += THREADS) {
         const int v = q / VW, u = q - v * VW;
         const int x = tx0 - VR + u, y = ty0 - VR + v;
@@ -301,11 +300,11 @@ __global__ void __launch_bounds__(THREADS) vg_moments_kernel(const VgParams p) {
         sg[q] = r;
         sl[q] = l;
     }
-    __syncthreads();
-    const int tx = tid % TW, ty = tid / TW;
-    const int px = tx0 + tx, py = ty0 + ty;
-    if (px >= W || py >= H) return;
-    const int cq = (ty + VR) * VW + tx + VR;
+}
+
+// Var_0 of the pixel (px, py) at region slot cq
+__device__ __forceinline__ float vg_var0(const VgParams& p, const float4* sg, const float* sl, int cq, int px, int py) {
+    const int W = (int)p.width, H = (int)p.height;
     const float4 gp = sg[cq];
     const float lp = sl[cq];
     float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
@@ -328,14 +327,29 @@ __global__ void __launch_bounds__(THREADS) vg_moments_kernel(const VgParams p) {
     }
     // (the centre tap has w = 1: sw >= 1)
     const float m1 = s1 / sw, m2 = s2 / sw;
+    return fmaxf(0.0f, m2 - m1 * m1);
+}
+
+__global__ void __launch_bounds__(THREADS) vg_moments_kernel(const VgParams p) {
+    __shared__ float4 sg[VPIX];
+    __shared__ float sl[VPIX];
+    const int W = (int)p.width, H = (int)p.height;
+    const int tx0 = (int)blockIdx.x * TW, ty0 = (int)blockIdx.y * TH;
+    const int tid = (int)threadIdx.x;
+    vg_stage(p, sg, sl, tx0, ty0, tid);
+    __syncthreads();
+    const int tx = tid % TW, ty = tid / TW;
+    const int px = tx0 + tx, py = ty0 + ty;
+    if (px >= W || py >= H) return;
+    const int cq = (ty + VR) * VW + tx + VR;
+    const float var0 = vg_var0(p, sg, sl, cq, px, py);
     const size_t pix = (size_t)py * p.width + (size_t)px;
     // the lane's own D_0 again from memory (the lines the staging loop just read): the same divisions,
     // so the luminance of this record is the staged one
     p.rout[pix] = make_float4(p.colour[3 * pix] / fmaxf(p.albedo[3 * pix], ALBEDO_FLOOR),
                               p.colour[3 * pix + 1] / fmaxf(p.albedo[3 * pix + 1], ALBEDO_FLOOR),
-                              p.colour[3 * pix + 2] / fmaxf(p.albedo[3 * pix + 2], ALBEDO_FLOOR),
-                              fmaxf(0.0f, m2 - m1 * m1));
-    p.gout[pix] = gp;
+                              p.colour[3 * pix + 2] / fmaxf(p.albedo[3 * pix + 2], ALBEDO_FLOOR), var0);
+    p.gout[pix] = sg[cq];
 }
 
 // One pass: atrous_kernel's tile (lattice pitch g, taps T points apart, halo 2 T points) over 16-byte
@@ -440,6 +454,43 @@ void launch_vg_pass(const VgParams& p, bool last, dim3 grid, hipStream_t stream)
     else hipLaunchKernelGGL((vg_atrous_kernel<T, false>), grid, dim3(THREADS), 0, stream, p);
 }
 
+// Enqueue passes 0 .. K-1 (p filled but rin, rout, pitch): pass i reads chain[i] and, unless it is the
+// last, writes chain[i + 1].
+void enqueue_vg_passes(VgParams p, uint32_t iterations, float4* const* chain, hipStream_t stream) {
+    const uint32_t lat = lattice_from();
+    for (uint32_t i = 0; i < iterations; ++i) {
+        const uint32_t step = 1u << i, g = step >= lat ? step : 1u;
+        p.rin = chain[i];
+        p.rout = chain[i + 1];
+        p.pitch = g;
+        const uint32_t lw = (p.width + g - 1) / g, lh = (p.height + g - 1) / g;
+        const dim3 grid(((lw + TW - 1) / TW) * g, ((lh + TH - 1) / TH) * g);
+        if (step / g == 1) launch_vg_pass<1>(p, i + 1 == iterations, grid, stream);
+        else if (step / g == 2) launch_vg_pass<2>(p, i + 1 == iterations, grid, stream);
+        else launch_vg_pass<4>(p, i + 1 == iterations, grid, stream);
+    }
+}
+
+// (the fields every vg launch shares)
+VgParams vg_params(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
+                   uint32_t rows, float sigma_luminance, float sigma_normal, float sigma_depth, float* out,
+                   float* out_variance) {
+    const double log2e = 1.4426950408889634;
+    VgParams p{};
+    p.colour = colour;
+    p.albedo = albedo;
+    p.normal = normal;
+    p.depth = depth;
+    p.cout = out;
+    p.vout = out_variance;
+    p.width = width;
+    p.height = rows;
+    p.sigma_l = sigma_luminance;
+    p.kn = (float)(log2e / ((double)sigma_normal * sigma_normal));
+    p.kz = (float)(log2e / ((double)sigma_depth * sigma_depth));
+    return p;
+}
+
 }  // namespace
 
 // The moments kernel reads the caller's colour and no pass does (the last one reads the albedo), so
@@ -453,39 +504,342 @@ void gpu_denoise_vg(DenoiseScratch* s, const float* colour, const float* albedo,
     int prev = 0;
     (void)hipGetDevice(&prev);
     check(hipSetDevice(s->device), "hipSetDevice");
-    const double log2e = 1.4426950408889634;
-    const uint32_t lat = lattice_from();
-    float4* bufs[2] = {(float4*)s->ping, (float4*)s->pong};
-    VgParams p{};
-    p.colour = colour;
-    p.albedo = albedo;
-    p.normal = normal;
-    p.depth = depth;
+    float4* const b0 = (float4*)s->ping;
+    float4* const b1 = (float4*)s->pong;
+    float4* const chain[6] = {b0, b1, b0, b1, b0, b1};
+    VgParams p = vg_params(colour, albedo, normal, depth, width, rows, sigma_luminance, sigma_normal, sigma_depth, out,
+                           out_variance);
     p.gin = s->guides;
     p.gout = s->guides;
-    p.cout = out;
-    p.vout = out_variance;
-    p.width = width;
-    p.height = rows;
-    p.sigma_l = sigma_luminance;
-    p.kn = (float)(log2e / ((double)sigma_normal * sigma_normal));
-    p.kz = (float)(log2e / ((double)sigma_depth * sigma_depth));
-    p.rout = bufs[0];
+    p.rout = b0;
     hipLaunchKernelGGL(vg_moments_kernel, dim3((width + TW - 1) / TW, (rows + TH - 1) / TH), dim3(THREADS), 0, stream, p);
-    for (uint32_t i = 0; i < iterations; ++i) {
-        const uint32_t step = 1u << i, g = step >= lat ? step : 1u;
-        p.rin = bufs[i & 1u];
-        p.rout = bufs[(i + 1u) & 1u];
-        p.pitch = g;
-        const uint32_t lw = (width + g - 1) / g, lh = (rows + g - 1) / g;
-        const dim3 grid(((lw + TW - 1) / TW) * g, ((lh + TH - 1) / TH) * g);
-        if (step / g == 1) launch_vg_pass<1>(p, i + 1 == iterations, grid, stream);
-        else if (step / g == 2) launch_vg_pass<2>(p, i + 1 == iterations, grid, stream);
-        else launch_vg_pass<4>(p, i + 1 == iterations, grid, stream);
-    }
+    enqueue_vg_passes(p, iterations, chain, stream);
     const hipError_t e = hipGetLastError();
     (void)hipSetDevice(prev);
     check(e, "denoise_vg launch");
+}
+
+// ---- temporal accumulation (SVGF's temporal half): one kernel in the moments kernel's place, then
+//      the passes above unchanged.  Formula: nrt.h (nrt_denoise_temporal).
+namespace {
+
+struct TemporalParams {
+    VgParams v;          // colour, albedo, normal, depth, width, height, kn, kz; rout = (I, V), gout = this frame's guides
+    const float4* pg;    // previous frame: guide records (N', Z')
+    const float4* ph;    // previous frame: (H'.rgb, .w unused here: the first pass's variance)
+    const float4* pm;    // previous frame: (m1', m2', n', 0)
+    float4* mout;        // this frame's (m1, m2, n, 0)
+    uint32_t have_prev;  // 0: every pixel's history is invalid (first frame, after a reset)
+    float c0[3], du[3], dv[3];  // this camera: top_left - look_from, pixel_delta_u, pixel_delta_v
+    float dl[3];         // look_from - look_from'
+    float t[3];          // M'^-1 (look_from - look_from')
+    float e[9];          // M'^-1 (M - M'), row-major: zero for equal cameras
+    float alpha_min, tau_z, tau_n;
+};
+
+// A workgroup computes 32 x 8 pixels.  Before the barrier every lane reads its own pixel, reprojects
+// it and issues the loads of its four taps, three 16-byte records each (guide, H', moments) from the
+// previous frame's buffers: neighbouring lanes reproject to neighbouring pixels, so a row of lanes
+// gathers from one or two rows of records, and the loads' latency runs under the staging of the
+// 38 x 14 region (vg_stage: the moments kernel's, the same LDS layout and conflict-free reads).
+//
+// The reprojection is evaluated relative to the pixel itself.  With k = Z / |d| and
+// (A, B, Cc) = M'^-1 r = k (x, y, 1) + k E (x, y, 1) + t,  E = M'^-1 (M - M'),  t = M'^-1 (look_from - look_from'),
+// and w = 1 / k:
+//   c = 1 + E_2 . (x, y, 1) + w t_2                     (= Cc / k, the same sign)
+//   u - x = (E_0 . (x, y, 1) + w t_0 - x (c - 1)) / c,  v - y likewise with E_1, t_1
+// so the rounding error of (u, v) is a few ulps of the motion, not of the pixel coordinate, and equal
+// cameras (E = 0, t = 0) give u = x, v = y exactly.  The host computes E and t in f64.
+//
+// After the barrier: tap tests, the blend, and Var_0 (vg_var0, 49 LDS taps) only in waves where the
+// ballot finds a lane with n < 4: a scalar branch, so a steady-state wave skips the loop whole.
+__global__ void __launch_bounds__(THREADS) temporal_kernel(const TemporalParams p) {
+    __shared__ float4 sg[VPIX];
+    __shared__ float sl[VPIX];
+    const int W = (int)p.v.width, H = (int)p.v.height;
+    const int tx0 = (int)blockIdx.x * TW, ty0 = (int)blockIdx.y * TH;
+    const int tid = (int)threadIdx.x;
+    const int tx = tid % TW, ty = tid / TW;
+    const int px = tx0 + tx, py = ty0 + ty;
+    const bool mine = px < W && py < H;
+    const size_t pix = mine ? (size_t)py * p.v.width + (size_t)px : 0;
+    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float4 tg[4] = {zero, zero, zero, zero}, th[4] = {zero, zero, zero, zero}, tm[4] = {zero, zero, zero, zero};
+    float4 gp = zero;
+    float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, fx = 0.0f, fy = 0.0f, zr = 0.0f;
+    bool reproj = false;
+    if (mine) {
+        gp = make_float4(p.v.normal[3 * pix], p.v.normal[3 * pix + 1], p.v.normal[3 * pix + 2], p.v.depth[pix]);
+        d0 = p.v.colour[3 * pix] / fmaxf(p.v.albedo[3 * pix], ALBEDO_FLOOR);
+        d1 = p.v.colour[3 * pix + 1] / fmaxf(p.v.albedo[3 * pix + 1], ALBEDO_FLOOR);
+        d2 = p.v.colour[3 * pix + 2] / fmaxf(p.v.albedo[3 * pix + 2], ALBEDO_FLOOR);
+        if (p.have_prev && gp.w > 0.0f) {
+            const float x = (float)px, y = (float)py;
+            const float r0 = fmaf(y, p.dv[0], fmaf(x, p.du[0], p.c0[0]));
+            const float r1 = fmaf(y, p.dv[1], fmaf(x, p.du[1], p.c0[1]));
+            const float r2 = fmaf(y, p.dv[2], fmaf(x, p.du[2], p.c0[2]));
+            const float len = sqrtf(r0 * r0 + r1 * r1 + r2 * r2);
+            const float k = gp.w / len, w = len / gp.w;
+            const float q0 = p.dl[0] + k * r0, q1 = p.dl[1] + k * r1, q2 = p.dl[2] + k * r2;  // r = P - look_from'
+            zr = sqrtf(q0 * q0 + q1 * q1 + q2 * q2);
+            const float e0 = fmaf(w, p.t[0], fmaf(y, p.e[1], fmaf(x, p.e[0], p.e[2])));
+            const float e1 = fmaf(w, p.t[1], fmaf(y, p.e[4], fmaf(x, p.e[3], p.e[5])));
+            const float e2 = fmaf(w, p.t[2], fmaf(y, p.e[7], fmaf(x, p.e[6], p.e[8])));
+            const float c = 1.0f + e2;
+            const float mu = (e0 - x * e2) / c, mv = (e1 - y * e2) / c;  // u - x, v - y
+            const float fu = floorf(mu), fv = floorf(mv);
+            const float bx = x + fu, by = y + fv;  // the first tap, still as floats: NaN and far-off motion fail here
+            if (c > 0.0f && bx >= -1.0f && bx <= (float)(W - 1) && by >= -1.0f && by <= (float)(H - 1)) {
+                reproj = true;
+                fx = mu - fu;
+                fy = mv - fv;
+                const int ix = (int)bx, iy = (int)by;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        if ((unsigned)(ix + i) < (unsigned)W && (unsigned)(iy + j) < (unsigned)H) {
+                            const size_t a = (size_t)(iy + j) * p.v.width + (size_t)(ix + i);
+                            tg[2 * j + i] = p.pg[a];
+                            th[2 * j + i] = p.ph[a];
+                            tm[2 * j + i] = p.pm[a];
+                        }
+                    }
+                }
+            }
+        }
+    }
+    vg_stage(p.v, sg, sl, tx0, ty0, tid);
+    __syncthreads();
+    if (!mine) return;
+    const int cq = (ty + VR) * VW + tx + VR;
+    const float l = sl[cq];
+    // taps in the fixed order (0,0), (1,0), (0,1), (1,1); a tap outside the image holds Z' = 0
+    const float b[4] = {(1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy};
+    float sb = 0.0f, h0 = 0.0f, h1 = 0.0f, h2 = 0.0f, s1 = 0.0f, s2 = 0.0f, nmin = 255.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float4 g = tg[i];
+        const bool ok = reproj && g.w > 0.0f && fabsf(g.w - zr) <= p.tau_z * zr &&
+                        g.x * gp.x + g.y * gp.y + g.z * gp.z >= p.tau_n;
+        const float bi = ok ? b[i] : 0.0f;
+        sb += bi;
+        h0 += bi * th[i].x;
+        h1 += bi * th[i].y;
+        h2 += bi * th[i].z;
+        s1 += bi * tm[i].x;
+        s2 += bi * tm[i].y;
+        nmin = ok ? fminf(nmin, tm[i].z) : nmin;
+    }
+    float i0 = d0, i1 = d1, i2 = d2, m1 = l, m2 = l * l, n = 1.0f;
+    if (sb >= 0.01f) {  // (sb > 0 needs a valid tap, so reproj holds and nmin is a tap's length)
+        n = fminf(1.0f + nmin, 255.0f);
+        const float alpha = fmaxf(p.alpha_min, 1.0f / n);
+        h0 /= sb;
+        h1 /= sb;
+        h2 /= sb;
+        s1 /= sb;
+        s2 /= sb;
+        i0 = h0 + alpha * (d0 - h0);
+        i1 = h1 + alpha * (d1 - h1);
+        i2 = h2 + alpha * (d2 - h2);
+        m1 = s1 + alpha * (l - s1);
+        m2 = s2 + alpha * (l * l - s2);
+    }
+    float var = fmaxf(0.0f, m2 - m1 * m1);
+    if (__ballot(n < 4.0f) != 0ull) {  // wave-uniform
+        const float var0 = vg_var0(p.v, sg, sl, cq, px, py);
+        if (n < 4.0f) var = var0 / n;
+    }
+    p.v.rout[pix] = make_float4(i0, i1, i2, var);
+    p.mout[pix] = make_float4(m1, m2, n, 0.0f);
+    p.v.gout[pix] = gp;
+}
+
+// 3 x 3 inverse in f64 (columns a, b, c), row-major; false when the determinant is below 1e-12 of the
+// product of the columns' lengths
+bool invert3(const double* a, const double* b, const double* c, double inv[9]) {
+    const double m[9] = {a[0], b[0], c[0], a[1], b[1], c[1], a[2], b[2], c[2]};
+    const double co[9] = {m[4] * m[8] - m[5] * m[7], m[2] * m[7] - m[1] * m[8], m[1] * m[5] - m[2] * m[4],
+                          m[5] * m[6] - m[3] * m[8], m[0] * m[8] - m[2] * m[6], m[2] * m[3] - m[0] * m[5],
+                          m[3] * m[7] - m[4] * m[6], m[1] * m[6] - m[0] * m[7], m[0] * m[4] - m[1] * m[3]};
+    const double det = m[0] * co[0] + m[1] * co[3] + m[2] * co[6];
+    auto len = [](const double* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+    const double scale = len(a) * len(b) * len(c);
+    if (!(std::fabs(det) > 1e-12 * scale) || !std::isfinite(det)) return false;
+    for (int i = 0; i < 9; ++i) inv[i] = co[i] / det;
+    return true;
+}
+
+}  // namespace
+
+// State (double-buffered by frame parity: a launch reads the previous records at gathered addresses
+// while it writes the new ones) and work buffers, 16 B per pixel each: 2 guides, 2 moments, H, 2 work.
+struct History {
+    uint32_t width = 0, rows = 0;
+    int device = -1;       // -1 until the first frame allocates
+    uint32_t frames = 0;   // since new / reset
+    uint32_t parity = 0;   // the buffers the last frame wrote
+    bool written = false;  // a frame has ever been enqueued (read() has something to copy)
+    TemporalCamera cam{};  // the last frame's
+    float4* guides[2] = {nullptr, nullptr};
+    float4* moments[2] = {nullptr, nullptr};
+    float4* hist = nullptr;
+    float4* work[2] = {nullptr, nullptr};
+    float* io = nullptr;   // the host entry point's staging (11 f32 per pixel), on first use
+};
+
+History* gpu_history_new(uint32_t width, uint32_t rows) {
+    auto* h = new History();
+    h->width = width;
+    h->rows = rows;
+    return h;
+}
+
+void gpu_history_free(History* h) {
+    if (!h) return;
+    if (h->device >= 0) {
+        int prev = 0;
+        (void)hipGetDevice(&prev);
+        (void)hipSetDevice(h->device);
+        for (void* b : {(void*)h->guides[0], (void*)h->guides[1], (void*)h->moments[0], (void*)h->moments[1],
+                        (void*)h->hist, (void*)h->work[0], (void*)h->work[1], (void*)h->io})
+            (void)hipFree(b);
+        (void)hipSetDevice(prev);
+    }
+    delete h;
+}
+
+void gpu_history_reset(History* h) { h->frames = 0; }
+int gpu_history_device(const History* h) { return h->device; }
+
+namespace {
+
+void history_alloc(History* h, int device) {
+    if (h->device >= 0) {
+        if (h->device != device) throw std::invalid_argument("the history lives on another device");
+        return;
+    }
+    const size_t bytes = (size_t)h->width * h->rows * sizeof(float4);
+    float4* b[7] = {};
+    for (auto& q : b) {
+        if (hipMalloc((void**)&q, bytes) != hipSuccess) {
+            for (auto& f : b) (void)hipFree(f);
+            throw std::runtime_error("HIP error in hipMalloc(history): out of device memory");
+        }
+    }
+    h->guides[0] = b[0], h->guides[1] = b[1], h->moments[0] = b[2], h->moments[1] = b[3];
+    h->hist = b[4], h->work[0] = b[5], h->work[1] = b[6];
+    h->device = device;
+}
+
+}  // namespace
+
+float* gpu_history_io(History* h, int device) {
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    check(hipSetDevice(device), "hipSetDevice");
+    hipError_t e = hipSuccess;
+    try {
+        history_alloc(h, device);
+        if (!h->io) e = hipMalloc((void**)&h->io, (size_t)h->width * h->rows * 11 * sizeof(float));
+    } catch (...) {
+        (void)hipSetDevice(prev);
+        throw;
+    }
+    (void)hipSetDevice(prev);
+    check(e, "hipMalloc(history staging)");
+    return h->io;
+}
+
+// temporal_kernel, then the K passes: pass 0 writes H (after the temporal kernel, the only reader of
+// H', has finished: the same stream), the later passes ping-pong between the work buffers.
+void gpu_denoise_temporal(History* h, int device, const TemporalCamera& cam, const float* colour, const float* albedo,
+                          const float* normal, const float* depth, uint32_t iterations, float sigma_luminance,
+                          float sigma_normal, float sigma_depth, float alpha_min, float tau_z, float tau_n, float* out,
+                          float* out_variance, void* stream_ptr) {
+    hipStream_t stream = (hipStream_t)stream_ptr;
+    TemporalParams t{};
+    const bool have_prev = h->frames > 0;
+    double c[3], inv[9];
+    for (int i = 0; i < 3; ++i) c[i] = cam.top_left[i] - cam.look_from[i];
+    // (this camera is the next frame's M': rejected now, the history never holds a singular one)
+    if (!invert3(cam.du, cam.dv, c, inv)) throw std::invalid_argument("denoise_temporal: the camera is singular");
+    if (have_prev) {
+        const TemporalCamera& o = h->cam;
+        double co[3];
+        for (int i = 0; i < 3; ++i) co[i] = o.top_left[i] - o.look_from[i];
+        invert3(o.du, o.dv, co, inv);
+        for (int r = 0; r < 3; ++r) {
+            double tr = 0.0, e0 = 0.0, e1 = 0.0, e2 = 0.0;
+            for (int i = 0; i < 3; ++i) {
+                tr += inv[3 * r + i] * (cam.look_from[i] - o.look_from[i]);
+                e0 += inv[3 * r + i] * (cam.du[i] - o.du[i]);
+                e1 += inv[3 * r + i] * (cam.dv[i] - o.dv[i]);
+                e2 += inv[3 * r + i] * (c[i] - co[i]);
+            }
+            t.t[r] = (float)tr;
+            t.e[3 * r] = (float)e0, t.e[3 * r + 1] = (float)e1, t.e[3 * r + 2] = (float)e2;
+        }
+        for (int i = 0; i < 3; ++i) t.dl[i] = (float)(cam.look_from[i] - o.look_from[i]);
+    }
+    for (int i = 0; i < 3; ++i) {
+        t.c0[i] = (float)(cam.top_left[i] - cam.look_from[i]);
+        t.du[i] = (float)cam.du[i];
+        t.dv[i] = (float)cam.dv[i];
+    }
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    check(hipSetDevice(device), "hipSetDevice");
+    try {
+        history_alloc(h, device);
+    } catch (...) {
+        (void)hipSetDevice(prev);
+        throw;
+    }
+    const uint32_t cur = h->parity ^ 1u;
+    t.v = vg_params(colour, albedo, normal, depth, h->width, h->rows, sigma_luminance, sigma_normal, sigma_depth, out,
+                    out_variance);
+    t.v.rout = h->work[0];
+    t.v.gout = h->guides[cur];
+    t.v.gin = h->guides[cur];
+    t.pg = h->guides[h->parity];
+    t.pm = h->moments[h->parity];
+    t.ph = h->hist;
+    t.mout = h->moments[cur];
+    t.have_prev = have_prev ? 1u : 0u;
+    t.alpha_min = alpha_min;
+    t.tau_z = tau_z;
+    t.tau_n = tau_n;
+    hipLaunchKernelGGL(temporal_kernel, dim3((h->width + TW - 1) / TW, (h->rows + TH - 1) / TH), dim3(THREADS), 0,
+                       stream, t);
+    float4* const chain[6] = {h->work[0], h->hist, h->work[0], h->work[1], h->work[0], h->work[1]};
+    enqueue_vg_passes(t.v, iterations, chain, stream);
+    const hipError_t e = hipGetLastError();
+    (void)hipSetDevice(prev);
+    check(e, "denoise_temporal launch");
+    h->parity = cur;
+    h->cam = cam;
+    h->frames += 1;
+    h->written = true;
+}
+
+// (m1, m2) and n of the last frame, after everything enqueued on the history's device has finished
+void gpu_history_read(History* h, float* moments, float* length) {
+    if (!h->written) throw std::invalid_argument("history_read: no frame yet");
+    const size_t n = (size_t)h->width * h->rows;
+    std::vector<float4> rec(n);
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    check(hipSetDevice(h->device), "hipSetDevice");
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(rec.data(), h->moments[h->parity], n * sizeof(float4), hipMemcpyDeviceToHost);
+    (void)hipSetDevice(prev);
+    check(e, "history_read");
+    for (size_t i = 0; i < n; ++i) {
+        if (moments) moments[2 * i] = rec[i].x, moments[2 * i + 1] = rec[i].y;
+        if (length) length[i] = rec[i].z;
+    }
 }
 
 }  // namespace nrt

@@ -66,6 +66,28 @@ void gpu_denoise(DenoiseScratch* s, const float* colour, const float* albedo, co
 void gpu_denoise_vg(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
                     uint32_t width, uint32_t rows, uint32_t iterations, float sigma_luminance, float sigma_normal,
                     float sigma_depth, float* out, float* out_variance, void* stream);
+// Temporal accumulation in front of the variance-guided passes (denoise.hip).  A History holds the
+// previous frame's camera, guide records, colour history, luminance moments and history length for
+// width x rows pixels, plus the work buffers of the passes: 112 B per pixel, allocated on `device`
+// by the first frame (gpu_history_io: now, plus the host entry point's staging of colour | albedo |
+// normal | depth | variance, 11 f32 per pixel).
+struct TemporalCamera {
+    double look_from[3], du[3], dv[3], top_left[3];
+};
+struct History;
+History* gpu_history_new(uint32_t width, uint32_t rows);
+void gpu_history_free(History* h);
+void gpu_history_reset(History* h);       // the next frame's history is invalid everywhere
+int gpu_history_device(const History* h);  // -1: nothing allocated yet
+float* gpu_history_io(History* h, int device);  // throws
+// Enqueue the temporal kernel and the `iterations` (2..5) passes on `stream`; out may be colour,
+// out_variance may be null.  std::invalid_argument for a singular camera or another device than the first frame's.
+void gpu_denoise_temporal(History* h, int device, const TemporalCamera& cam, const float* colour, const float* albedo,
+                          const float* normal, const float* depth, uint32_t iterations, float sigma_luminance,
+                          float sigma_normal, float sigma_depth, float alpha_min, float tau_z, float tau_n, float* out,
+                          float* out_variance, void* stream);
+// Waits for the device, then copies out the last frame's (m1, m2) (2 f32 per pixel) and n (1 f32); either may be null.
+void gpu_history_read(History* h, float* moments, float* length);
 // First `count` draws of `lanes` consecutive streams starting at stream0 (tests).
 struct JitCounts {
     uint64_t compiled, launches, failed, compile_ns, disk_hits, load_retries;

@@ -83,6 +83,11 @@ class _DenoiseVgOpts(C.Structure):
                 ("sigma_depth", C.c_float)]
 
 
+class _DenoiseTemporalOpts(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float), ("alpha_min", C.c_float), ("tau_z", C.c_float), ("tau_n", C.c_float)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64)
 
 # Every symbol include/nrt.h declares, with its ctypes signature.
@@ -144,6 +149,14 @@ SIGNATURES = {
                                  C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nrt_denoise_vg_device": (C.c_int, [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseVgOpts), C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrt_history_new": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_int32]),
+    "nrt_history_free": (None, [C.c_void_p]),
+    "nrt_history_reset": (C.c_int, [C.c_void_p]),
+    "nrt_denoise_temporal": (C.c_int, [C.c_void_p, C.POINTER(_Camera)] + [C.POINTER(C.c_float)] * 4 +
+                             [C.POINTER(_DenoiseTemporalOpts), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nrt_denoise_temporal_device": (C.c_int, [C.c_void_p, C.POINTER(_Camera)] + [C.c_void_p] * 4 +
+                                    [C.POINTER(_DenoiseTemporalOpts), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrt_history_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nrt_rows_selected": (C.c_uint32, [C.c_uint32, C.POINTER(_RenderOpts)]),
     "nrt_scene_upload": (C.c_int, [C.c_void_p, C.c_int32]),
     "nrt_scene_stats_get": (C.c_int, [C.c_void_p, C.POINTER(_SceneStats)]),
@@ -433,17 +446,20 @@ class Scene:
         over devices device .. device+N-1 (device -1: 0), one RCCL gather (nrt_render_opts.gpus).
         denoise = True (or the number of passes, 1..5): the frame, then its feature buffers
         (render_aov), then the a-trous filter (nrt.denoise) over both; whole frames on one device.
-        denoise = "variance": the same chain with the variance-guided filter (nrt.denoise_vg)."""
+        denoise = "variance": the same chain with the variance-guided filter (nrt.denoise_vg).
+        denoise = a History: the same chain with History.denoise and this camera, frame after frame."""
         cam = camera or self.camera
         if cam is None:
             raise ValueError("no camera")
         if isinstance(denoise, str) and denoise != "variance":
-            raise ValueError(f"denoise must be False, True, 1..5 or 'variance', not {denoise!r}")
+            raise ValueError(f"denoise must be False, True, 1..5, 'variance' or a History, not {denoise!r}")
         if denoise:
             if row_stride > 1 or row_offset:
                 raise ValueError("denoise filters whole frames: row_offset 0 and row_stride 1")
             frame = self.render(cam, precision, rng, device, progress=progress, trace=trace, gpus=gpus)
             aov = self.render_aov(cam, trace=trace, device=device)
+            if isinstance(denoise, History):
+                return denoise.denoise(frame, camera=cam, out=frame, **aov)
             if denoise == "variance":
                 return denoise_vg(frame, device=device, out=frame, **aov)
             return globals()["denoise"](frame, iterations=5 if denoise is True else int(denoise), device=device,
@@ -712,6 +728,86 @@ def denoise_vg(colour: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth
     _check(lib().nrt_denoise_vg(ptr(c), ptr(a), ptr(n), ptr(z), c.shape[1], c.shape[0], C.byref(d), device, ptr(out),
                                 ptr(v) if v is not None else None))
     return out
+
+
+class History:
+    """Temporal accumulation in front of the variance-guided filter (nrt_history, nrt_denoise_temporal): SVGF
+    over a sequence of frames of one static scene.  Each call reprojects the previous call's colour history and
+    luminance moments through the two cameras, blends this frame in, and runs the variance-guided passes.
+    `frames`: the frames since the history was made or reset."""
+
+    def __init__(self, width: int, rows: int, device: int = -1):
+        self.width, self.rows, self.frames = width, rows, 0
+        self._h = C.c_void_p(lib().nrt_history_new(width, rows, device))
+        if not self._h.value:
+            raise NrtError(-1, _err())
+
+    def close(self) -> None:
+        if self._h and self._h.value:
+            lib().nrt_history_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _opts(iterations, sigma_luminance=4.0, sigma_normal=0.3, sigma_depth=0.5, alpha_min=0.2, tau_z=0.1, tau_n=0.9):
+        return _DenoiseTemporalOpts(iterations, sigma_luminance, sigma_normal, sigma_depth, alpha_min, tau_z, tau_n)
+
+    def reset(self) -> None:
+        """The next frame starts a new history (nrt_history_reset)."""
+        _check(lib().nrt_history_reset(self._h))
+        self.frames = 0
+
+    def denoise(self, frame: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth: np.ndarray, camera: Camera,
+                iterations: int = 5, variance_out: Optional[np.ndarray] = None, out: Optional[np.ndarray] = None,
+                **sigmas) -> np.ndarray:
+        """The next frame of the sequence (nrt_denoise_temporal): buffers as `denoise_vg`, `camera` the one the
+        frame and its feature buffers were rendered with; iterations 2..5; sigmas: sigma_luminance,
+        sigma_normal, sigma_depth, alpha_min, tau_z, tau_n."""
+        def f32(a):
+            return a if a.dtype == np.float32 and a.flags.c_contiguous else np.ascontiguousarray(a, dtype=np.float32)
+
+        c, a, n, z = f32(frame), f32(albedo), f32(normal), f32(depth)
+        shape = (self.rows, self.width, 3)
+        if c.shape != shape or a.shape != shape or n.shape != shape or z.shape != shape[:2]:
+            raise NrtError(-1, f"History.denoise: frame {c.shape}, albedo {a.shape}, normal {n.shape}, depth {z.shape} "
+                               f"do not describe one {shape} frame")
+        if out is None:
+            out = np.empty_like(c)
+        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != shape:
+            raise NrtError(-1, "History.denoise: out must be a contiguous float32 array of the frame's shape")
+        v = variance_out
+        if v is not None and (v.dtype != np.float32 or not v.flags.c_contiguous or v.shape != shape[:2]):
+            raise NrtError(-1, "History.denoise: variance_out must be a contiguous float32 array of shape (rows, W)")
+        ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
+        _check(lib().nrt_denoise_temporal(self._h, C.byref(camera._c()), ptr(c), ptr(a), ptr(n), ptr(z),
+                                          C.byref(self._opts(iterations, **sigmas)), ptr(out),
+                                          ptr(v) if v is not None else None))
+        self.frames += 1
+        return out
+
+    def denoise_device(self, colour_ptr: int, albedo_ptr: int, normal_ptr: int, depth_ptr: int, camera: Camera,
+                       out_ptr: int, variance_ptr: int = 0, iterations: int = 5, stream: int = 0, **sigmas) -> None:
+        """Enqueue the next frame over device memory on the history's device (nrt_denoise_temporal_device);
+        out_ptr may be colour_ptr, variance_ptr may be 0."""
+        _check(lib().nrt_denoise_temporal_device(self._h, C.byref(camera._c()), C.c_void_p(colour_ptr),
+                                                 C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr), C.c_void_p(depth_ptr),
+                                                 C.byref(self._opts(iterations, **sigmas)), C.c_void_p(out_ptr),
+                                                 C.c_void_p(variance_ptr), C.c_void_p(stream)))
+        self.frames += 1
+
+    def read(self):
+        """(moments, length) of the last frame (nrt_history_read): (rows, W, 2) float32 m1, m2 of the demodulated
+        luminance and (rows, W) float32 history lengths; waits for the device."""
+        m = np.empty((self.rows, self.width, 2), np.float32)
+        n = np.empty((self.rows, self.width), np.float32)
+        _check(lib().nrt_history_read(self._h, m.ctypes.data_as(C.POINTER(C.c_float)),
+                                      n.ctypes.data_as(C.POINTER(C.c_float))))
+        return m, n
 
 
 def debug_rng(rng: str, stream0: int, lanes: int, count: int, sample: int = 0) -> np.ndarray:
