@@ -1,5 +1,6 @@
 """Shared test helpers: the oracle (test infrastructure) and scene fixtures."""
 import contextlib
+import functools
 import os
 import subprocess
 import tempfile
@@ -76,3 +77,40 @@ def oracle_render(tree, threads=None, rows=(0, 1), stats=False, spp=None, var=Fa
 def oracle_dump(tree):
     ensure_oracle()
     return subprocess.run([ORACLE_BIN, "dump", tree], check=True, capture_output=True, text=True).stdout
+
+
+# ---- the synthetic frame of the two spatial denoiser tests (test_denoise.py, test_denoise_vg.py)
+PATCH = (slice(5, 12), slice(24, 35))  # 7 x 11, across the tile seams y = 8 and x = 32
+
+
+def synthetic(H, W, floor=False):
+    """Two regions split by a slanted line (normals, depth ramps), a 3-row miss band, a 4-pixel
+    checker albedo, colour = base * albedo * (1 + 0.5 gauss); float32, as the library takes them.
+    floor: the albedo of PATCH is (0, 5e-4, 2e-3), exactly zero, below the filters' floor of 1e-3 and just
+    above it, and its colour base * max(albedo, 1e-3) * (1 + 0.5 gauss): the demodulated colour stays O(1)."""
+    rng = np.random.default_rng(1000 * H + W)
+    ys, xs = np.mgrid[0:H, 0:W]
+    left = xs < W * 0.45 + ys * 0.2
+    N = np.where(left[..., None], [0, 0, 1.0], [0.6, 0, 0.8])
+    Z = np.where(left, 2.0 + 0.01 * xs, 3.5 + 0.02 * ys)
+    N[:3], Z[:3] = 0, 0
+    A = np.where(((xs // 4 + ys // 4) % 2)[..., None] == 0, [0.8, 0.3, 0.2], [0.2, 0.7, 0.9])
+    A[:3] = [0.1, 0.2, 0.3]
+    if floor:
+        A[PATCH] = [0.0, 5e-4, 2e-3]
+    C = np.abs(np.where(left[..., None], 0.7, 0.25) * (np.maximum(A, 1e-3) if floor else A)
+               * (1 + 0.5 * rng.standard_normal((H, W, 3))))
+    return tuple(np.ascontiguousarray(x, dtype=np.float32) for x in (C, A, N, Z))
+
+
+def synthetic_cases(reference):
+    """case(shape, K, floor=False, **sigmas) -> (frame, reference(*frame, K, **sigmas)): computed once per
+    session, shared by the tests that need it, and read-only."""
+    @functools.lru_cache(maxsize=None)
+    def case(shape, K, floor=False, **sigmas):
+        frame = synthetic(*shape, floor=floor)
+        ref = reference(*frame, K, **sigmas)
+        for x in (*frame, *(ref if isinstance(ref, tuple) else (ref,))):
+            x.setflags(write=False)
+        return frame, ref
+    return case

@@ -5,14 +5,21 @@ and the plumbing from Scene.render(denoise=True) down to the device entry points
 Filter tolerance, max|out - ref| <= 5e-5 max|ref|: the f32 exponent argument carries ~1.7e-6
 absolute error where the weight still matters (e <~ 20), i.e. ~1.2e-6 relative on a weight and
 ~4e-6 on a convex weighted mean per pass; passes do not amplify, five give ~2e-5; the bound is 2.5x
-that.  The same formula in numpy f32 differs from f64 by 5.5e-7 on these inputs."""
+that.  The same formula in numpy f32 differs from f64 by 5.5e-7 on these inputs (6.5e-7 at 129 x 513 and
+131 x 530).  Nothing in the derivation depends on the shape.
+
+Shapes.  A pass of step s >= 2 runs on the s^2 lattices (x mod s, y mod s) in tiles of 32 x 8 lattice points:
+129 x 513 = (8 16 + 1) x (32 16 + 1) gives lattice 0 one more tile than the others at every step (a tile seam
+in both axes and the kernel's "tile past the end" return at steps 2 .. 16), 131 x 530 a partly filled last
+tile in every lattice; 9 x 33 is a second image-space tile of one column, 6 x 9 a frame whose every pixel
+lacks taps, 1 x 1 the centre tap alone."""
 import math
 
 import numpy as np
 import pytest
 
 import nrt
-from helpers import in_golden
+from helpers import PATCH, in_golden, synthetic_cases
 
 H5 = (1 / 16, 1 / 4, 3 / 8, 1 / 4, 1 / 16)
 
@@ -41,27 +48,14 @@ def atrous_f64(C, A, N, Z, K, sc=0.6, sn=0.3, sz=0.5):
     return D * a
 
 
-def synthetic(H, W):
-    """Two regions split by a slanted line (normals, depth ramps), a 3-row miss band, a 4-pixel
-    checker albedo, colour = base * albedo * (1 + 0.5 gauss); float32, as the library takes them."""
-    rng = np.random.default_rng(1000 * H + W)
-    ys, xs = np.mgrid[0:H, 0:W]
-    left = xs < W * 0.45 + ys * 0.2
-    N = np.where(left[..., None], [0, 0, 1.0], [0.6, 0, 0.8])
-    Z = np.where(left, 2.0 + 0.01 * xs, 3.5 + 0.02 * ys)
-    N[:3], Z[:3] = 0, 0
-    A = np.where(((xs // 4 + ys // 4) % 2)[..., None] == 0, [0.8, 0.3, 0.2], [0.2, 0.7, 0.9])
-    A[:3] = [0.1, 0.2, 0.3]
-    C = np.abs(np.where(left[..., None], 0.7, 0.25) * A * (1 + 0.5 * rng.standard_normal((H, W, 3))))
-    return tuple(np.ascontiguousarray(x, dtype=np.float32) for x in (C, A, N, Z))
+case = synthetic_cases(atrous_f64)  # (frame, f64 reference), computed once per session and read-only
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("K", [1, 3, 5])
-@pytest.mark.parametrize("shape", [(29, 37), (45, 70)])
+@pytest.mark.parametrize("shape", [(29, 37), (45, 70), (129, 513), (131, 530), (1, 1), (6, 9), (9, 33)])
 def test_filter_matches_f64_definition(shape, K):
-    C, A, N, Z = synthetic(*shape)
-    ref = atrous_f64(C, A, N, Z, K)
+    (C, A, N, Z), ref = case(shape, K)
     out = nrt.denoise(C, A, N, Z, iterations=K)
     err, scale = np.abs(out - ref).max(), np.abs(ref).max()
     print(f"a-trous {shape} K={K}: max|out - ref| = {err:.3e} = {err / scale:.3e} max|ref|")
@@ -70,6 +64,70 @@ def test_filter_matches_f64_definition(shape, K):
     inplace = C.copy()
     assert nrt.denoise(inplace, A, N, Z, iterations=K, out=inplace) is inplace
     assert np.array_equal(inplace, out)
+
+
+@pytest.mark.gpu
+def test_tile_split_knob_gives_the_same_bits(monkeypatch):
+    """NRT_ATROUS_LATTICE = first step on lattice tiles; the steps below it take image-space tiles whose taps are
+    T = step points apart: 8 runs atrous_kernel<2> at step 2 and <4> at step 4, 4 runs <2> at step 2, and 1, 2
+    and unset no image-space tile past step 1.  Same taps in the same order per pixel: the same bits."""
+    (C, A, N, Z), _ = case((129, 513), 5)
+    monkeypatch.delenv("NRT_ATROUS_LATTICE", raising=False)
+    want = nrt.denoise(C, A, N, Z, iterations=5)
+    for v in ("1", "2", "4", "8"):
+        monkeypatch.setenv("NRT_ATROUS_LATTICE", v)
+        got = nrt.denoise(C, A, N, Z, iterations=5)
+        print(f"a-trous (129, 513) K=5 NRT_ATROUS_LATTICE={v}: {(got != want).sum()} of {want.size} values differ "
+              f"from the default split, max {np.abs(got - want).max():.3e}")
+        assert np.array_equal(got, want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 5])
+@pytest.mark.parametrize("shape", [(29, 37), (129, 513)])
+def test_albedo_floor(shape, K):
+    """Albedo 0 and 5e-4 are floored to 1e-3 when demodulating and when remodulating alike, and 2e-3 is left alone:
+    D_0 stays O(1) there, and the output is D_K a with a = max(albedo, 1e-3) (not 0, not D_K times the raw albedo,
+    and no other floor).  The derivation's bound applies to D_K, so on every channel of the patch the error is within
+    5e-5 max|D_K| a: 1e-3 and 2e-3 of the whole-frame bound."""
+    (C, A, N, Z), ref = case(shape, K, floor=True)
+    out = nrt.denoise(C, A, N, Z, iterations=K)
+    err, scale = np.abs(out - ref).max(), np.abs(ref).max()
+    a = np.maximum(A, 1e-3).astype(np.float64)
+    dscale, perr = np.abs(ref / a).max(), (np.abs(out - ref) / a)[PATCH].max(axis=(0, 1))
+    print(f"a-trous floor {shape} K={K}: max|out - ref| = {err:.3e} = {err / scale:.3e} max|ref|; patch channels "
+          f"(albedo 0, 5e-4, 2e-3): " + ", ".join(f"{e / dscale:.3e}" for e in perr) + " of max(albedo, 1e-3) max|D_K|")
+    assert np.isfinite(out).all()
+    assert err <= 5e-5 * scale
+    assert (A[PATCH] == np.float32([0.0, 5e-4, 2e-3])).all() and (ref[PATCH] > 0).all()
+    assert (out[PATCH] > 0).all()
+    assert (perr <= 5e-5 * dscale).all()
+
+
+NON_DEFAULT = dict(sigma_color=0.25, sigma_normal=0.7, sigma_depth=1.3)
+F64_NAMES = dict(sigma_color="sc", sigma_normal="sn", sigma_depth="sz")
+
+
+@pytest.mark.gpu
+def test_sigmas_are_honoured_and_nonpositive_selects_the_default():
+    shape, K = (45, 70), 3
+    (C, A, N, Z), ref0 = case(shape, K)
+    _, ref = case(shape, K, **{F64_NAMES[k]: v for k, v in NON_DEFAULT.items()})
+    tol = 5e-5 * np.abs(ref).max()
+    assert np.abs(ref - ref0).max() > 100 * tol  # the case would not pass with the sigmas ignored,
+    for k in NON_DEFAULT:  # nor with any one of them: a filter within tol of `one` is then 9 tol or more from ref
+        _, one = case(shape, K, **{F64_NAMES[j]: v for j, v in NON_DEFAULT.items() if j != k})
+        assert np.abs(ref - one).max() > 10 * tol
+    out = nrt.denoise(C, A, N, Z, iterations=K, **NON_DEFAULT)
+    err = np.abs(out - ref).max()
+    print(f"a-trous {shape} K={K} {NON_DEFAULT}: max|out - ref| = {err:.3e} = {err / np.abs(ref).max():.3e} max|ref|")
+    assert err <= tol
+    want = nrt.denoise(C, A, N, Z, iterations=K)
+    assert np.abs(want - ref0).max() <= 5e-5 * np.abs(ref0).max()
+    for v in (0.0, -1.0):
+        for k in NON_DEFAULT:
+            assert np.array_equal(nrt.denoise(C, A, N, Z, iterations=K, **{k: v}), want)
+        assert np.array_equal(nrt.denoise(C, A, N, Z, iterations=K, **dict.fromkeys(NON_DEFAULT, v)), want)
 
 
 @pytest.mark.gpu

@@ -7,7 +7,12 @@ and moments <= 5e-5 max m2 (every blend and pass is a convex mean of values thes
 exactly.  The reference marks as fragile every pixel where a decision of the definition sits within 1e-3
 (relative) of its threshold: a tap's depth and normal tests, Cc > 0, sb >= 0.01, and u, v within 1e-3 of an
 integer.  Equal cameras give u = x, v = y exactly on both sides (E = 0, t = 0 are exact zeros), so there the
-last test has nothing to flip and is not applied.  Measured on an MI355X: DESIGN.md (temporal accumulation)."""
+last test has nothing to flip and is not applied.  Measured on an MI355X: DESIGN.md (temporal accumulation).
+
+Cases A and B run 5 and 3 frames at the default options, where alpha = max(alpha_min, 1 / n) is 1 / n, n stays far
+from its cap and the depth test decides nearly every tap the normal test would; the tests after them make the
+clamp, the cap of 255, tau_n alone and non-default alpha_min, tau_z, tau_n decide, each after asserting on the
+definition itself that the option changes the result."""
 import dataclasses
 
 import numpy as np
@@ -220,6 +225,176 @@ def test_case_b_general_motion_temporal_state():
         assert suspect.mean() <= 0.05
         check_state(f"temporal B frame {i}", hist, st, suspect)
     assert (st["n"] == 3).mean() >= 0.30
+
+
+@pytest.mark.gpu
+def test_long_zero_motion_history_alpha_min_clamp_and_length_cap():
+    """258 frames of one camera: every pixel's single tap (weight 1) is valid, so n = min(i + 1, 255) at frame
+    index i, alpha = max(0.2, 1 / n) is the clamp from index 5 on (1 / 6 < 0.2), and the cap of 255 binds from index
+    254 on.  Every frame is compared; the blend is a contraction (alpha >= 0.2), so the f32 state's error does not
+    grow with the sequence and the file's bounds apply to every frame."""
+    shape, K, count = (6, 9), 2, 258
+    cam = cameras_a(*shape)[0]
+    frames = [planes_frame(cam, PLANES_A, 9000 + i) for i in range(count)]
+    st = free = None
+    for C, A, N, Z in frames[:8]:  # alpha = 1 / n alone is another filter by frame 7
+        st, free = temporal_f64(st, cam, C, A, N, Z, K)[2], temporal_f64(free, cam, C, A, N, Z, K, amin=0.0)[2]
+    assert np.abs(st["m1"] - free["m1"]).max() > 100 * 5e-5 * st["m2"].max()
+    hist, st, worst = nrt.History(shape[1], shape[0]), None, np.zeros(3)
+    for i, (C, A, N, Z) in enumerate(frames):
+        ref, ref_var, st, frag, _, v0 = temporal_f64(st, cam, C, A, N, Z, K)
+        assert not frag.any() and (st["n"] == min(i + 1, 255)).all()
+        out = hist.denoise(C, A, N, Z, cam, iterations=K, variance_out=(var := np.full(shape, np.nan, np.float32)))
+        (m, n), scale = hist.read(), np.abs(ref).max()
+        err, verr = np.abs(out - ref).max(), np.abs(var - ref_var).max()
+        merr = max(np.abs(m[..., 0] - st["m1"]).max(), np.abs(m[..., 1] - st["m2"]).max())
+        worst = np.maximum(worst, [err / scale, verr / v0, merr / st["m2"].max()])
+        if i in (5, 6, 7, 127, 128, 253, 254, 255, 257):
+            print(f"temporal long {shape} K={K} frame {i}: n = {n.min():.0f} .. {n.max():.0f}; colour err "
+                  f"{err / scale:.3e} max|ref|; variance err {verr / v0:.3e} max Var_0; moments err "
+                  f"{merr / st['m2'].max():.3e} max m2")
+        assert np.array_equal(n, st["n"]), f"frame {i}"
+        assert err <= 5e-5 * scale and verr <= 5e-5 * v0 and merr <= 5e-5 * st["m2"].max(), f"frame {i}"
+    print(f"temporal long {shape} K={K}: worst of {count} frames: colour {worst[0]:.3e}, variance {worst[1]:.3e}, "
+          f"moments {worst[2]:.3e}")
+    assert st["n"].min() == 255 and hist.frames == count
+
+
+@pytest.mark.gpu
+def test_case_b_non_default_alpha_min_and_tau_z():
+    """Case B's three cameras with alpha_min = 0.6 (it binds at n = 2 and 3) and tau_z = 0.02 (the slanted plane's
+    depth changes by more than 2 % between neighbouring taps where the default's 10 % accepts them)."""
+    shape, opts, refs = (45, 70), dict(amin=0.6, tz=0.02), []
+    st = dflt = lazy = None
+    suspect = np.zeros(shape, bool)
+    for i, cam in enumerate(cameras_b(*shape)):
+        frame = planes_frame(cam, PLANES_B, 500 + i)
+        dflt, lazy = temporal_f64(dflt, cam, *frame, 2)[2], temporal_f64(lazy, cam, *frame, 2, tz=0.02)[2]
+        _, _, st, frag, foot, _ = temporal_f64(st, cam, *frame, 2, **opts)
+        suspect = frag | ((foot >= 0) & suspect.reshape(-1)[np.maximum(foot, 0)]).any(0)  # dilated through the gather
+        assert suspect.mean() <= 0.05
+        refs.append((cam, frame, st, suspect))
+    differ = (st["n"] != dflt["n"])[~suspect].mean()
+    mdiff = np.abs(st["m1"] - lazy["m1"])[~suspect].max()
+    print(f"temporal B {opts}: suspect {suspect.mean():.3%}; n differs from the default thresholds' on {differ:.1%} of "
+          f"the rest; m1 differs from alpha_min 0.2's by {mdiff / st['m2'].max():.3e} max m2")
+    assert differ >= 0.10                          # tau_z matters,
+    assert mdiff > 100 * 5e-5 * st["m2"].max()     # and so does alpha_min
+    hist = nrt.History(shape[1], shape[0])
+    for i, (cam, frame, st, suspect) in enumerate(refs):
+        hist.denoise(*frame, cam, iterations=2, alpha_min=0.6, tau_z=0.02)
+        check_state(f"temporal B {opts} frame {i}", hist, st, suspect)
+
+
+@pytest.mark.gpu
+def test_normal_and_depth_thresholds_each_decide_taps():
+    """Equal cameras: one tap of weight 1 per pixel, the pixel itself.  The second frame has the first one's
+    feature buffers but for two rectangles: in one the normals are turned so that N' . N = 0.95, in the other the
+    depth is 1.05 times the first frame's (|Z' - z'| / z' = 0.0476).  With (tau_n, tau_z) = (0.9, 0.1) every tap
+    passes both tests; with (0.97, 0.02) the normal test alone rejects the first rectangle's taps and the depth test
+    alone the second's.  All of 0.95, 1 and 0.0476, 0 are far from the four thresholds: no fragile pixel."""
+    shape, K = (45, 70), 2
+    cam = cameras_a(*shape)[0]
+    C0, A, N0, Z0 = planes_frame(cam, PLANES_A, 4500)
+    C1 = planes_frame(cam, PLANES_A, 4501)[0]
+    assert (N0 == [0, 0, 1]).all() and (Z0 > 0).all()
+    turned, scaled = (slice(10, 20), slice(8, 30)), (slice(25, 40), slice(40, 65))
+    N1, Z1, rejected = N0.copy(), Z0.copy(), np.zeros(shape, bool)
+    N1[turned] = [np.sqrt(1 - 0.95 ** 2), 0, 0.95]
+    Z1[scaled] *= np.float32(1.05)
+    rejected[turned] = rejected[scaled] = True
+    for (tn, tz), want_n in (((0.9, 0.1), np.full(shape, 2.0)), ((0.97, 0.02), np.where(rejected, 1.0, 2.0))):
+        _, _, st, frag0, _, _ = temporal_f64(None, cam, C0, A, N0, Z0, K, tn=tn, tz=tz)
+        ref, ref_var, st, frag, _, v0 = temporal_f64(st, cam, C1, A, N1, Z1, K, tn=tn, tz=tz)
+        assert not frag0.any() and not frag.any()
+        assert np.array_equal(st["n"], want_n)
+        hist = nrt.History(shape[1], shape[0])
+        hist.denoise(C0, A, N0, Z0, cam, iterations=K, tau_n=tn, tau_z=tz)
+        var = np.full(shape, np.nan, np.float32)
+        out = hist.denoise(C1, A, N1, Z1, cam, iterations=K, variance_out=var, tau_n=tn, tau_z=tz)
+        err, verr = np.abs(out - ref).max(), np.abs(var - ref_var).max()
+        print(f"temporal thresholds tau_n={tn} tau_z={tz}: colour err {err:.3e} = {err / np.abs(ref).max():.3e} "
+              f"max|ref|; variance err {verr:.3e} = {verr / v0:.3e} max Var_0; n = 1 on {(st['n'] == 1).sum()} pixels")
+        check_state(f"temporal thresholds tau_n={tn} tau_z={tz}", hist, st, frag)
+        assert err <= 5e-5 * np.abs(ref).max()
+        assert verr <= 5e-5 * v0
+
+
+def run(seq, K, **opts):
+    """The sequence [(camera, frame), ...] on a fresh history: the last frame's out, variance, moments, n."""
+    shape = seq[0][1][3].shape
+    hist = nrt.History(shape[1], shape[0])
+    for cam, frame in seq:
+        var = np.full(shape, np.nan, np.float32)
+        out = hist.denoise(*frame, cam, iterations=K, variance_out=var, **opts)
+    return (out, var, *hist.read())
+
+
+def definition(seq, K, **opts):
+    """The same sequence through the definition: the last frame's out and state."""
+    st = None
+    with np.errstate(all="ignore"):  # (a literal sigma of -1 may overflow)
+        for cam, frame in seq:
+            out, _, st, _, _, _ = temporal_f64(st, cam, *frame, K, **opts)
+    return out, st
+
+
+def seq_a(count):
+    """The first `count` frames of case A at 45 x 70 (the camera moves)."""
+    return [(cam, planes_frame(cam, PLANES_A, 4500 + i)) for i, cam in enumerate(cameras_a(45, 70)[:count])]
+
+
+@pytest.mark.gpu
+def test_nonpositive_option_selects_the_default():
+    """An option of 0 or -1 gives the default call's bits, on a sequence where the literal value would not: each
+    option has a sequence on which the definition, given the literal 0 or -1, differs from the definition at the
+    default, which is asserted first.
+      alpha_min: 8 frames of one 6 x 9 camera, n = 8: alpha = max(0.2, 1 / 8) is the clamp, max(0, 1 / 8) is not.
+      tau_n: equal cameras at 45 x 70, the first frame's normals turned to N' . N = 0.5 in a rectangle: 0.9 rejects
+        those taps (n = 1), 0 and -1 accept them (n = 2).
+      tau_z: two frames of case A: 0 accepts only an exactly equal depth, -1 nothing.
+      sigmas: the same two frames, and for sigma_normal the turned-normal pair (case A's normals are all equal); -1 is
+        another filter (or none: the luminance weight overflows); a literal 0 divides by zero on both sides, so
+        only the bits are compared for it."""
+    K = 2
+    cam6 = cameras_a(6, 9)[0]
+    clamp = [(cam6, planes_frame(cam6, PLANES_A, 9000 + i)) for i in range(8)]
+    cam = cameras_a(45, 70)[0]
+    C0, A, N0, Z0 = planes_frame(cam, PLANES_A, 4500)
+    turned, Nt = (slice(10, 20), slice(8, 30)), N0.copy()
+    Nt[turned] = [np.sqrt(1 - 0.5 ** 2), 0, 0.5]
+    normals = [(cam, (C0, A, Nt, Z0)), (cam, (planes_frame(cam, PLANES_A, 4501)[0], A, N0, Z0))]
+    moving = seq_a(2)
+    f64 = dict(alpha_min="amin", tau_z="tz", tau_n="tn", sigma_luminance="sl", sigma_normal="sn", sigma_depth="sz")
+    for seq, names in ((clamp, ["alpha_min"]), (normals, ["tau_n", "sigma_normal"]),
+                       (moving, ["tau_z", "sigma_luminance", "sigma_depth"])):
+        ref, st = definition(seq, K)
+        tol = 5e-5 * st["m2"].max()
+        want = run(seq, K)
+        assert np.array_equal(want[3], st["n"])  # the default call is the definition's at the default
+        for k in names:
+            for v in (0.0, -1.0):
+                if not (k.startswith("sigma") and v == 0.0):
+                    lit, lst = definition(seq, K, **{f64[k]: v})
+                    if k in ("tau_n", "tau_z"):
+                        assert (lst["n"] != st["n"]).mean() >= 0.05, (k, v)
+                    elif k == "alpha_min":
+                        assert np.abs(lst["m1"] - st["m1"]).max() > 100 * tol, (k, v)
+                    else:
+                        assert not np.abs(lit - ref).max() <= 100 * 5e-5 * np.abs(ref).max(), (k, v)
+                for a, b in zip(run(seq, K, **{k: v}), want):
+                    assert np.array_equal(a, b), (k, v)
+
+
+@pytest.mark.gpu
+def test_tile_split_knob_gives_the_same_bits(monkeypatch):
+    """The temporal chain's passes are the variance-guided filter's (test_denoise_vg.py has the knob's meaning): with
+    NRT_ATROUS_LATTICE=8 the steps 2 and 4 of K = 5 take image-space tiles, and the bits are the default's."""
+    monkeypatch.delenv("NRT_ATROUS_LATTICE", raising=False)
+    want = run(seq_a(2), 5)
+    monkeypatch.setenv("NRT_ATROUS_LATTICE", "8")
+    for a, b in zip(run(seq_a(2), 5), want):
+        assert np.array_equal(a, b)
 
 
 @pytest.mark.gpu
