@@ -705,34 +705,74 @@ struct DenoiseArgs {
     float sigma_color, sigma_normal, sigma_depth;  // (sigma_color: the variance-guided filter's sigma_luminance)
 };
 
-DenoiseArgs denoise_args(const void* c, const void* a, const void* n, const void* z, const void* out, uint32_t width,
-                         uint32_t rows, const nrt_denoise_opts* o, float sigma_color_default = 0.6f) {
-    if (!c || !a || !n || !z || !out) throw std::invalid_argument("null argument");
+void check_frame_size(uint32_t width, uint32_t rows, const char* who) {
     // (the lattice grid of step 16 has rows / 8 + 16 workgroup rows: below HIP's 65 536)
     if (width == 0 || rows == 0 || width > (1u << 24) || rows > (1u << 18))
-        throw std::invalid_argument("denoise: width in 1..2^24 and rows in 1..2^18");
-    DenoiseArgs d{5u, sigma_color_default, 0.3f, 0.5f};
-    if (o) {
-        if (o->iterations > 5) throw std::invalid_argument("denoise: iterations must be 1..5 (0 = 5)");
-        if (o->iterations) d.iterations = o->iterations;
-        if (o->sigma_color > 0.0f) d.sigma_color = o->sigma_color;
-        if (o->sigma_normal > 0.0f) d.sigma_normal = o->sigma_normal;
-        if (o->sigma_depth > 0.0f) d.sigma_depth = o->sigma_depth;
-    }
-    return d;
+        throw std::invalid_argument(std::string(who) + ": width in 1..2^24 and rows in 1..2^18");
 }
 
-DenoiseArgs denoise_vg_args(const void* c, const void* a, const void* n, const void* z, const void* out,
-                            uint32_t width, uint32_t rows, const nrt_denoise_vg_opts* o) {
-    nrt_denoise_opts d{};
-    if (o) d = nrt_denoise_opts{o->iterations, o->sigma_luminance, o->sigma_normal, o->sigma_depth};
-    return denoise_args(c, a, n, z, out, width, rows, o ? &d : nullptr, 4.0f);
+// The checks and defaults the three filters share; the option values as the caller's struct holds them (all 0
+// without one): non-positive selects the default.
+DenoiseArgs denoise_args(const void* c, const void* a, const void* n, const void* z, const void* out, uint32_t width,
+                         uint32_t rows, uint32_t iterations, float sigma_color, float sigma_normal, float sigma_depth,
+                         float sigma_color_default) {
+    if (!c || !a || !n || !z || !out) throw std::invalid_argument("null argument");
+    check_frame_size(width, rows, "denoise");
+    if (iterations > 5) throw std::invalid_argument("denoise: iterations must be 1..5 (0 = 5)");
+    return DenoiseArgs{iterations ? iterations : 5u, sigma_color > 0.0f ? sigma_color : sigma_color_default,
+                       sigma_normal > 0.0f ? sigma_normal : 0.3f, sigma_depth > 0.0f ? sigma_depth : 0.5f};
 }
 
 int device_or_current(int32_t device) {
     nrt_render_opts o{};
     o.device = device;
     return resolve_device(&o);
+}
+
+// Device staging of a host entry point's frame: colour | albedo | normal | depth | the rest of `floats` f32 per pixel.
+// Owns the allocation unless it is handed one (the history's persistent buffer).
+struct FrameStaging {
+    const size_t n;
+    const int dev;
+    float* const lent;
+    float* const d;
+    FrameStaging(size_t pixels, int device, size_t floats, float* have = nullptr)
+        : n(pixels), dev(device), lent(have), d(have ? have : (float*)device_alloc(pixels * floats * sizeof(float), device)) {}
+    ~FrameStaging() {
+        if (!lent) device_free(d, dev);
+    }
+    FrameStaging(const FrameStaging&) = delete;
+    FrameStaging& operator=(const FrameStaging&) = delete;
+    float* colour() const { return d; }
+    float* albedo() const { return d + 3 * n; }
+    float* normal() const { return d + 6 * n; }
+    float* depth() const { return d + 9 * n; }
+    float* rest() const { return d + 10 * n; }
+    void upload(const float* c, const float* a, const float* nn, const float* z) const {
+        device_copy_from_host(colour(), c, n * 3 * sizeof(float), dev);
+        device_copy_from_host(albedo(), a, n * 3 * sizeof(float), dev);
+        device_copy_from_host(normal(), nn, n * 3 * sizeof(float), dev);
+        device_copy_from_host(depth(), z, n * sizeof(float), dev);
+    }
+    // after everything enqueued on the device has finished: `channels` f32 per pixel from src
+    void download(float* dst, const float* src, size_t channels) const {
+        device_sync(dev);
+        if (dst) device_copy_to_host(dst, src, n * channels * sizeof(float), dev);
+    }
+};
+
+using ScratchPtr = std::unique_ptr<DenoiseScratch, decltype(&gpu_denoise_scratch_free)>;
+
+// The scene's scratch of one filter (slots: index = HIP ordinal) on `dev`, grown to `pixels` if need be.
+DenoiseScratch* scene_scratch(const nrt_scene* scene, std::vector<DenoiseScratch*> nrt_scene::*slots, int dev,
+                              size_t pixels, size_t rec_bytes) {
+    nrt_scene* s = const_cast<nrt_scene*>(scene);
+    std::lock_guard<std::mutex> lock(s->mu);
+    std::vector<DenoiseScratch*>& v = s->*slots;
+    if ((int)v.size() <= dev) v.resize((size_t)dev + 1, nullptr);
+    DenoiseScratch* have = v[(size_t)dev];
+    v[(size_t)dev] = nullptr;  // (gpu_denoise_scratch frees `have` before it can throw)
+    return v[(size_t)dev] = gpu_denoise_scratch(have, pixels, dev, rec_bytes);
 }
 
 // Checks shared by the two feature-pass calls; the launch parameters of the rows opts selects.
@@ -794,18 +834,11 @@ int nrt_denoise_device(const nrt_scene* scene, const float* dev_colour, const fl
                        const nrt_denoise_opts* dopts, int32_t device, float* dev_out, void* hip_stream) {
     return guarded(NRT_E_DEVICE, [&]() {
         if (!scene) throw std::invalid_argument("null argument");
-        const DenoiseArgs a = denoise_args(dev_colour, dev_albedo, dev_normal, dev_depth, dev_out, width, rows, dopts);
+        const nrt_denoise_opts o = dopts ? *dopts : nrt_denoise_opts{};
+        const DenoiseArgs a = denoise_args(dev_colour, dev_albedo, dev_normal, dev_depth, dev_out, width, rows,
+                                           o.iterations, o.sigma_color, o.sigma_normal, o.sigma_depth, 0.6f);
         const int dev = device_or_current(device);
-        nrt_scene* s = const_cast<nrt_scene*>(scene);
-        DenoiseScratch* scratch = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(s->mu);
-            if ((int)s->denoise.size() <= dev) s->denoise.resize((size_t)dev + 1, nullptr);
-            DenoiseScratch*& slot = s->denoise[(size_t)dev];
-            DenoiseScratch* have = slot;
-            slot = nullptr;  // (gpu_denoise_scratch frees `have` before it can throw)
-            scratch = slot = gpu_denoise_scratch(have, (size_t)width * rows, dev);
-        }
+        DenoiseScratch* scratch = scene_scratch(scene, &nrt_scene::denoise, dev, (size_t)width * rows, 12);
         gpu_denoise(scratch, dev_colour, dev_albedo, dev_normal, dev_depth, width, rows, a.iterations, a.sigma_color,
                     a.sigma_normal, a.sigma_depth, dev_out, hip_stream);
         return NRT_OK;
@@ -815,31 +848,19 @@ int nrt_denoise_device(const nrt_scene* scene, const float* dev_colour, const fl
 int nrt_denoise(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
                 uint32_t rows, const nrt_denoise_opts* dopts, int32_t device, float* out) {
     return guarded(NRT_E_DEVICE, [&]() {
-        const DenoiseArgs a = denoise_args(colour, albedo, normal, depth, out, width, rows, dopts);
+        const nrt_denoise_opts o = dopts ? *dopts : nrt_denoise_opts{};
+        const DenoiseArgs a = denoise_args(colour, albedo, normal, depth, out, width, rows, o.iterations, o.sigma_color,
+                                           o.sigma_normal, o.sigma_depth, 0.6f);
         const int dev = device_or_current(device);
         const size_t n = (size_t)width * rows;
-        float* d = nullptr;  // colour | albedo | normal | depth | out (out == colour: filtered in place)
-        DenoiseScratch* scratch = nullptr;
         const bool in_place = out == colour;
-        try {
-            d = (float*)device_alloc(n * (in_place ? 10 : 13) * sizeof(float), dev);
-            float* const dout = in_place ? d : d + 10 * n;
-            scratch = gpu_denoise_scratch(nullptr, n, dev);
-            device_copy_from_host(d, colour, n * 3 * sizeof(float), dev);
-            device_copy_from_host(d + 3 * n, albedo, n * 3 * sizeof(float), dev);
-            device_copy_from_host(d + 6 * n, normal, n * 3 * sizeof(float), dev);
-            device_copy_from_host(d + 9 * n, depth, n * sizeof(float), dev);
-            gpu_denoise(scratch, d, d + 3 * n, d + 6 * n, d + 9 * n, width, rows, a.iterations, a.sigma_color,
-                        a.sigma_normal, a.sigma_depth, dout, nullptr);
-            device_sync(dev);
-            device_copy_to_host(out, dout, n * 3 * sizeof(float), dev);
-        } catch (...) {
-            gpu_denoise_scratch_free(scratch);
-            if (d) device_free(d, dev);
-            throw;
-        }
-        gpu_denoise_scratch_free(scratch);
-        device_free(d, dev);
+        const FrameStaging st(n, dev, in_place ? 10 : 13);  // ... | out (out == colour: filtered in place)
+        float* const dout = in_place ? st.colour() : st.rest();
+        const ScratchPtr scratch(gpu_denoise_scratch(nullptr, n, dev, 12), gpu_denoise_scratch_free);
+        st.upload(colour, albedo, normal, depth);
+        gpu_denoise(scratch.get(), st.colour(), st.albedo(), st.normal(), st.depth(), width, rows, a.iterations,
+                    a.sigma_color, a.sigma_normal, a.sigma_depth, dout, nullptr);
+        st.download(out, dout, 3);
         return NRT_OK;
     });
 }
@@ -850,18 +871,11 @@ int nrt_denoise_vg_device(const nrt_scene* scene, const float* dev_colour, const
                           void* hip_stream) {
     return guarded(NRT_E_DEVICE, [&]() {
         if (!scene) throw std::invalid_argument("null argument");
-        const DenoiseArgs a = denoise_vg_args(dev_colour, dev_albedo, dev_normal, dev_depth, dev_out, width, rows, dopts);
+        const nrt_denoise_vg_opts o = dopts ? *dopts : nrt_denoise_vg_opts{};
+        const DenoiseArgs a = denoise_args(dev_colour, dev_albedo, dev_normal, dev_depth, dev_out, width, rows,
+                                           o.iterations, o.sigma_luminance, o.sigma_normal, o.sigma_depth, 4.0f);
         const int dev = device_or_current(device);
-        nrt_scene* s = const_cast<nrt_scene*>(scene);
-        DenoiseScratch* scratch = nullptr;
-        {
-            std::lock_guard<std::mutex> lock(s->mu);
-            if ((int)s->denoise_vg.size() <= dev) s->denoise_vg.resize((size_t)dev + 1, nullptr);
-            DenoiseScratch*& slot = s->denoise_vg[(size_t)dev];
-            DenoiseScratch* have = slot;
-            slot = nullptr;  // (gpu_denoise_scratch frees `have` before it can throw)
-            scratch = slot = gpu_denoise_scratch(have, (size_t)width * rows, dev, 16);
-        }
+        DenoiseScratch* scratch = scene_scratch(scene, &nrt_scene::denoise_vg, dev, (size_t)width * rows, 16);
         gpu_denoise_vg(scratch, dev_colour, dev_albedo, dev_normal, dev_depth, width, rows, a.iterations, a.sigma_color,
                        a.sigma_normal, a.sigma_depth, dev_out, dev_out_variance, hip_stream);
         return NRT_OK;
@@ -871,30 +885,19 @@ int nrt_denoise_vg_device(const nrt_scene* scene, const float* dev_colour, const
 int nrt_denoise_vg(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
                    uint32_t rows, const nrt_denoise_vg_opts* dopts, int32_t device, float* out, float* out_variance) {
     return guarded(NRT_E_DEVICE, [&]() {
-        const DenoiseArgs a = denoise_vg_args(colour, albedo, normal, depth, out, width, rows, dopts);
+        const nrt_denoise_vg_opts o = dopts ? *dopts : nrt_denoise_vg_opts{};
+        const DenoiseArgs a = denoise_args(colour, albedo, normal, depth, out, width, rows, o.iterations,
+                                           o.sigma_luminance, o.sigma_normal, o.sigma_depth, 4.0f);
         const int dev = device_or_current(device);
         const size_t n = (size_t)width * rows;
-        float* d = nullptr;  // colour, filtered in place | albedo | normal | depth | variance
-        DenoiseScratch* scratch = nullptr;
-        try {
-            d = (float*)device_alloc(n * 11 * sizeof(float), dev);
-            scratch = gpu_denoise_scratch(nullptr, n, dev, 16);
-            device_copy_from_host(d, colour, n * 3 * sizeof(float), dev);
-            device_copy_from_host(d + 3 * n, albedo, n * 3 * sizeof(float), dev);
-            device_copy_from_host(d + 6 * n, normal, n * 3 * sizeof(float), dev);
-            device_copy_from_host(d + 9 * n, depth, n * sizeof(float), dev);
-            gpu_denoise_vg(scratch, d, d + 3 * n, d + 6 * n, d + 9 * n, width, rows, a.iterations, a.sigma_color,
-                           a.sigma_normal, a.sigma_depth, d, out_variance ? d + 10 * n : nullptr, nullptr);
-            device_sync(dev);
-            device_copy_to_host(out, d, n * 3 * sizeof(float), dev);
-            if (out_variance) device_copy_to_host(out_variance, d + 10 * n, n * sizeof(float), dev);
-        } catch (...) {
-            gpu_denoise_scratch_free(scratch);
-            if (d) device_free(d, dev);
-            throw;
-        }
-        gpu_denoise_scratch_free(scratch);
-        device_free(d, dev);
+        const FrameStaging st(n, dev, 11);  // colour, filtered in place | ... | variance
+        const ScratchPtr scratch(gpu_denoise_scratch(nullptr, n, dev, 16), gpu_denoise_scratch_free);
+        st.upload(colour, albedo, normal, depth);
+        gpu_denoise_vg(scratch.get(), st.colour(), st.albedo(), st.normal(), st.depth(), width, rows, a.iterations,
+                       a.sigma_color, a.sigma_normal, a.sigma_depth, st.colour(), out_variance ? st.rest() : nullptr,
+                       nullptr);
+        st.download(out, st.colour(), 3);
+        st.download(out_variance, st.rest(), 1);
         return NRT_OK;
     });
 }
@@ -922,9 +925,10 @@ TemporalArgs temporal_args(const nrt_history* h, const nrt_camera* camera, const
                            const float* n, const float* z, const nrt_denoise_temporal_opts* o, const float* out,
                            const float* var) {
     if (!h || !camera) throw std::invalid_argument("null argument");
-    nrt_denoise_vg_opts v{};
-    if (o) v = nrt_denoise_vg_opts{o->iterations, o->sigma_luminance, o->sigma_normal, o->sigma_depth};
-    TemporalArgs t{denoise_vg_args(c, a, n, z, out, h->width, h->rows, o ? &v : nullptr), 0.2f, 0.1f, 0.9f, {}};
+    const nrt_denoise_temporal_opts v = o ? *o : nrt_denoise_temporal_opts{};
+    TemporalArgs t{denoise_args(c, a, n, z, out, h->width, h->rows, v.iterations, v.sigma_luminance, v.sigma_normal,
+                                v.sigma_depth, 4.0f),
+                   0.2f, 0.1f, 0.9f, {}};
     if (t.d.iterations < 2) throw std::invalid_argument("denoise_temporal: iterations must be 2..5 (0 = 5)");
     if (camera->width != h->width || camera->height != h->rows)
         throw std::invalid_argument("denoise_temporal: the camera's size is not the history's");
@@ -966,8 +970,7 @@ void temporal_run(nrt_history* h, const TemporalArgs& t, int dev, const float* c
 nrt_history* nrt_history_new(uint32_t width, uint32_t rows, int32_t device) {
     nrt_history* h = nullptr;
     guarded(NRT_E_INVALID, [&]() {
-        if (width == 0 || rows == 0 || width > (1u << 24) || rows > (1u << 18))
-            throw std::invalid_argument("history: width in 1..2^24 and rows in 1..2^18");
+        check_frame_size(width, rows, "history");
         auto p = std::make_unique<nrt_history>();
         p->h = gpu_history_new(width, rows);
         p->width = width, p->rows = rows, p->device = device;
@@ -1007,15 +1010,12 @@ int nrt_denoise_temporal(nrt_history* history, const nrt_camera* camera, const f
         const TemporalArgs t = temporal_args(history, camera, colour, albedo, normal, depth, opts, out, out_variance);
         const int dev = history_device(history);
         const size_t n = (size_t)history->width * history->rows;
-        float* d = gpu_history_io(history->h, dev);  // colour, filtered in place | albedo | normal | depth | variance
-        device_copy_from_host(d, colour, n * 3 * sizeof(float), dev);
-        device_copy_from_host(d + 3 * n, albedo, n * 3 * sizeof(float), dev);
-        device_copy_from_host(d + 6 * n, normal, n * 3 * sizeof(float), dev);
-        device_copy_from_host(d + 9 * n, depth, n * sizeof(float), dev);
-        temporal_run(history, t, dev, d, d + 3 * n, d + 6 * n, d + 9 * n, d, out_variance ? d + 10 * n : nullptr, nullptr);
-        device_sync(dev);
-        device_copy_to_host(out, d, n * 3 * sizeof(float), dev);
-        if (out_variance) device_copy_to_host(out_variance, d + 10 * n, n * sizeof(float), dev);
+        const FrameStaging st(n, dev, 11, gpu_history_io(history->h, dev));  // colour, filtered in place | ... | variance
+        st.upload(colour, albedo, normal, depth);
+        temporal_run(history, t, dev, st.colour(), st.albedo(), st.normal(), st.depth(), st.colour(),
+                     out_variance ? st.rest() : nullptr, nullptr);
+        st.download(out, st.colour(), 3);
+        st.download(out_variance, st.rest(), 1);
         return NRT_OK;
     });
 }

@@ -15,11 +15,15 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <initializer_list>
+#include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gpu.hpp"
+#include "hip_util.hpp"
 
 namespace nrt {
 
@@ -29,8 +33,10 @@ constexpr int TW = 32, TH = 8;  // outputs per workgroup: one per lane, a wave =
 constexpr int THREADS = TW * TH;
 constexpr float ALBEDO_FLOOR = 1e-3f;
 
+constexpr double LOG2E = 1.4426950408889634;
+
 struct AtrousParams {
-    const float* cin;     // FIRST: the caller's colour; else D_i (3 f32 per pixel)
+    const float* colour;  // FIRST: the caller's colour; else D_i (3 f32 per pixel)
     const float* albedo;  // FIRST (demodulation) and LAST (remodulation)
     const float* normal;  // FIRST
     const float* depth;   // FIRST
@@ -42,11 +48,108 @@ struct AtrousParams {
     float kc, kn, kz;     // log2(e) / (sigma_c 2^-i)^2, log2(e) / sigma_n^2, log2(e) / sigma_z^2
 };
 
-// One pass.  A workgroup computes TW x TH points of the lattice (x mod g, y mod g) = (lx, ly) and
-// stages them plus a halo of 2 T points in LDS, T = s / g: with g = 1 that is an image-space tile
+struct VgParams {
+    const float* colour;  // moments kernel: the caller's colour
+    const float* albedo;  // moments kernel (demodulation) and LAST (remodulation)
+    const float* normal;  // moments kernel
+    const float* depth;   // moments kernel
+    const float4* rin;    // passes: (D_i.rgb, Var_i)
+    const float4* gin;    // passes: the guide records (normal.xyz, depth) the moments kernel packed
+    float4* rout;         // moments kernel: (D_0, Var_0); passes but LAST: (D_{i+1}, Var_{i+1})
+    float4* gout;         // moments kernel
+    float* cout;          // LAST: the caller's output, 3 f32 per pixel
+    float* vout;          // LAST: the caller's variance buffer, 1 f32 per pixel, or null
+    uint32_t width, height;
+    uint32_t pitch;       // as AtrousParams
+    float sigma_l, kn, kz;  // sigma_l, log2(e) / sigma_n^2, log2(e) / sigma_z^2
+};
+
+// The fields the two filters' parameters share and every launch of a chain keeps (not gin, gout, pitch).  The
+// structs keep their own layouts rather than embed a common one: the kernels' argument loads, and with them the
+// generated code, stay what they were.
+template <class P>
+P frame_params(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
+               uint32_t rows, float sigma_normal, float sigma_depth, float* out) {
+    P p{};
+    p.colour = colour;
+    p.albedo = albedo;
+    p.normal = normal;
+    p.depth = depth;
+    p.cout = out;
+    p.width = width;
+    p.height = rows;
+    p.kn = (float)(LOG2E / ((double)sigma_normal * sigma_normal));
+    p.kz = (float)(LOG2E / ((double)sigma_depth * sigma_depth));
+    return p;
+}
+
+// 0 <= v < n.  (The tests of x and of y stay two calls joined by && or || where they are used: joined inside a
+// helper they compile to other code.)
+__device__ __forceinline__ bool in_range(int v, int n) { return (unsigned)v < (unsigned)n; }
+
+// colour / max(albedo, floor) and its inverse, per channel value i
+__device__ __forceinline__ float demodulate(const float* colour, const float* albedo, size_t i) {
+    return colour[i] / fmaxf(albedo[i], ALBEDO_FLOOR);
+}
+__device__ __forceinline__ float remodulate(float d, const float* albedo, size_t i) {
+    return d * fmaxf(albedo[i], ALBEDO_FLOOR);
+}
+
+// the guide record (normal.xyz, depth) of pixel a from the feature buffers
+template <class P>
+__device__ __forceinline__ float4 load_guide(const P& p, size_t a) {
+    return make_float4(p.normal[3 * a], p.normal[3 * a + 1], p.normal[3 * a + 2], p.depth[a]);
+}
+
+// h = (1/16, 1/4, 3/8, 1/4, 1/16) and the 3 x 3 prefilter's (1/4, 1/2, 1/4)
+__device__ __forceinline__ float h5(int i) {
+    constexpr float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    return hk[i];
+}
+__device__ __forceinline__ float g3(int i) {
+    constexpr float gk[3] = {0.25f, 0.5f, 0.25f};
+    return gk[i];
+}
+
+// The tile of one workgroup of a pass.  It computes TW x TH points of the lattice (x mod g, y mod g) = (lx, ly)
+// and stages them plus a halo of 2 T points in LDS, T = s / g: with g = 1 that is an image-space tile
 // with its 2 s halo (T = s = 1, 2, 4), with g = s the tile of an independent lattice of the
-// step-s pass (T = 1), whose halo stays 2 points however large s is.  Region row-major,
-// RW = TW + 4 T wide:
+// step-s pass (T = 1), whose halo stays 2 points however large s is.  Region row-major, RW = TW + 4 T wide.
+template <int T>
+struct LatticeTile {
+    static constexpr int RW = TW + 4 * T, RH = TH + 4 * T, NPIX = RW * RH;
+    const uint32_t width;
+    const int g, s, W, H, lx, ly, tx0, ty0;  // s = T g: the step; tx0, ty0: lattice coordinates
+    template <class P>
+    __device__ __forceinline__ explicit LatticeTile(const P& p)
+        : width(p.width), g((int)p.pitch), s(T * g), W((int)p.width), H((int)p.height),
+          lx((int)(blockIdx.x % p.pitch)), ly((int)(blockIdx.y % p.pitch)),
+          tx0((int)(blockIdx.x / p.pitch) * TW), ty0((int)(blockIdx.y / p.pitch) * TH) {}
+    // the tile's first pixel: (uniform) not in the image for a tile past the end of a short lattice
+    __device__ __forceinline__ int x0() const { return lx + tx0 * g; }
+    __device__ __forceinline__ int y0() const { return ly + ty0 * g; }
+    // region slot q = v RW + u -> pixel (lx + (tx0 - 2 T + u) g, ly + (ty0 - 2 T + v) g), maybe outside the image
+    __device__ __forceinline__ int2 slot_pixel(int q) const {
+        const int v = q / RW, u = q - v * RW;
+        return make_int2(lx + (tx0 - 2 * T + u) * g, ly + (ty0 - 2 * T + v) * g);
+    }
+    __device__ __forceinline__ size_t index(int2 xy) const { return (size_t)xy.y * width + (size_t)xy.x; }
+    // A lane's own point (tx, ty), its pixel (px, py) and its region slot cq; tap (dx, dy) of the step: its slot,
+    // and whether its row / column is in the image.
+    struct Lane {
+        const LatticeTile& t;
+        const int tx, ty, px, py, cq;
+        __device__ __forceinline__ Lane(const LatticeTile& tile, int tid)
+            : t(tile), tx(tid % TW), ty(tid / TW), px(t.lx + (t.tx0 + tx) * t.g), py(t.ly + (t.ty0 + ty) * t.g),
+              cq((ty + 2 * T) * RW + tx + 2 * T) {}
+        __device__ __forceinline__ size_t pix() const { return (size_t)py * t.width + (size_t)px; }
+        __device__ __forceinline__ int tap(int dx, int dy) const { return cq + dy * T * RW + dx * T; }
+        __device__ __forceinline__ bool row_ok(int dy) const { return in_range(py + dy * t.s, t.H); }
+        __device__ __forceinline__ bool col_ok(int dx) const { return in_range(px + dx * t.s, t.W); }
+    };
+};
+
+// One pass over the packed colour.  LDS, over LatticeTile's region:
 //   sc[3 (v RW + u) + c]  colour, packed as in memory: the staging loop's element e is written to
 //                         word e (lane-contiguous, no conflict), and a tap read is word 3 u + const
 //                         over the 32 lanes of a row: 3 is odd, so the 32 lanes hit 32 banks;
@@ -54,61 +157,53 @@ struct AtrousParams {
 // Slots outside the image hold zeros and their taps get weight 0 from the coordinate test.
 template <int T, bool FIRST, bool LAST>
 __global__ void __launch_bounds__(THREADS) atrous_kernel(const AtrousParams p) {
-    constexpr int RW = TW + 4 * T, RH = TH + 4 * T, NPIX = RW * RH;
-    __shared__ float4 sg[NPIX];
-    __shared__ float sc[3 * NPIX];
-    const int g = (int)p.pitch, W = (int)p.width, H = (int)p.height;
-    const int lx = (int)(blockIdx.x % p.pitch), ly = (int)(blockIdx.y % p.pitch);
-    const int tx0 = (int)(blockIdx.x / p.pitch) * TW, ty0 = (int)(blockIdx.y / p.pitch) * TH;  // lattice coordinates
-    if (lx + tx0 * g >= W || ly + ty0 * g >= H) return;  // (uniform) a tile past the end of a short lattice
+    using Tile = LatticeTile<T>;
+    __shared__ float4 sg[Tile::NPIX];
+    __shared__ float sc[3 * Tile::NPIX];
+    const Tile t(p);
+    if (t.x0() >= t.W || t.y0() >= t.H) return;
     const int tid = (int)threadIdx.x;
-    // region slot (u, v) -> pixel (lx + (tx0 - 2 T + u) g, ly + (ty0 - 2 T + v) g)
-    for (int e = tid; e < 3 * NPIX; e += THREADS) {
-        const int q = e / 3, c = e - 3 * q, v = q / RW, u = q - v * RW;
-        const int x = lx + (tx0 - 2 * T + u) * g, y = ly + (ty0 - 2 * T + v) * g;
+    for (int e = tid; e < 3 * Tile::NPIX; e += THREADS) {
+        const int q = e / 3, c = e - 3 * q;
+        const int2 xy = t.slot_pixel(q);
         float val = 0.0f;
-        if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
-            const size_t a = ((size_t)y * p.width + (size_t)x) * 3u + (size_t)c;
-            val = p.cin[a];
-            if constexpr (FIRST) val = val / fmaxf(p.albedo[a], ALBEDO_FLOOR);
+        if (in_range(xy.x, t.W) && in_range(xy.y, t.H)) {
+            const size_t a = t.index(xy) * 3u + (size_t)c;
+            if constexpr (FIRST) val = demodulate(p.colour, p.albedo, a);
+            else val = p.colour[a];
         }
         sc[e] = val;
     }
-    for (int q = tid; q < NPIX; q += THREADS) {
-        const int v = q / RW, u = q - v * RW;
-        const int x = lx + (tx0 - 2 * T + u) * g, y = ly + (ty0 - 2 * T + v) * g;
+    for (int q = tid; q < Tile::NPIX; q += THREADS) {
+        const int2 xy = t.slot_pixel(q);
         float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
-            const size_t a = (size_t)y * p.width + (size_t)x;
-            if constexpr (FIRST) r = make_float4(p.normal[3 * a], p.normal[3 * a + 1], p.normal[3 * a + 2], p.depth[a]);
-            else r = p.gin[a];
+        if (in_range(xy.x, t.W) && in_range(xy.y, t.H)) {
+            if constexpr (FIRST) r = load_guide(p, t.index(xy));
+            else r = p.gin[t.index(xy)];
         }
         sg[q] = r;
     }
     __syncthreads();
-    const int tx = tid % TW, ty = tid / TW;
-    const int px = lx + (tx0 + tx) * g, py = ly + (ty0 + ty) * g;
-    if (px >= W || py >= H) return;
-    const int s = T * g;
-    const int cq = (ty + 2 * T) * RW + tx + 2 * T;
+    const typename Tile::Lane me(t, tid);
+    if (me.px >= t.W || me.py >= t.H) return;
+    const int cq = me.cq;
     const float4 gp = sg[cq];
     const float c0 = sc[3 * cq], c1 = sc[3 * cq + 1], c2 = sc[3 * cq + 2];
-    constexpr float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     float sw = 0.0f, a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
-        const bool oky = (unsigned)(py + dy * s) < (unsigned)H;
+        const bool oky = me.row_ok(dy);
 #pragma unroll
         for (int dx = -2; dx <= 2; ++dx) {
-            const bool ok = oky && (unsigned)(px + dx * s) < (unsigned)W;
-            const int q = cq + dy * T * RW + dx * T;
+            const bool ok = oky && me.col_ok(dx);
+            const int q = me.tap(dx, dy);
             const float4 gq = sg[q];
             const float q0 = sc[3 * q], q1 = sc[3 * q + 1], q2 = sc[3 * q + 2];
             const float d0 = c0 - q0, d1 = c1 - q1, d2 = c2 - q2;
             const float n0 = gp.x - gq.x, n1 = gp.y - gq.y, n2 = gp.z - gq.z, dz = gp.w - gq.w;
             const float e = (d0 * d0 + d1 * d1 + d2 * d2) * p.kc + (n0 * n0 + n1 * n1 + n2 * n2) * p.kn + dz * dz * p.kz;
             // exp(-e) as one v_exp_f32 (the constants carry log2(e))
-            const float w = ok ? hk[dx + 2] * hk[dy + 2] * __builtin_amdgcn_exp2f(-e) : 0.0f;
+            const float w = ok ? h5(dx + 2) * h5(dy + 2) * __builtin_amdgcn_exp2f(-e) : 0.0f;
             sw += w;
             a0 += w * q0;
             a1 += w * q1;
@@ -117,11 +212,11 @@ __global__ void __launch_bounds__(THREADS) atrous_kernel(const AtrousParams p) {
     }
     // (the centre tap has e = 0: sw >= 9/64)
     float o0 = a0 / sw, o1 = a1 / sw, o2 = a2 / sw;
-    const size_t pix = (size_t)py * p.width + (size_t)px;
+    const size_t pix = me.pix();
     if constexpr (LAST) {
-        o0 *= fmaxf(p.albedo[3 * pix], ALBEDO_FLOOR);
-        o1 *= fmaxf(p.albedo[3 * pix + 1], ALBEDO_FLOOR);
-        o2 *= fmaxf(p.albedo[3 * pix + 2], ALBEDO_FLOOR);
+        o0 = remodulate(o0, p.albedo, 3 * pix);
+        o1 = remodulate(o1, p.albedo, 3 * pix + 1);
+        o2 = remodulate(o2, p.albedo, 3 * pix + 2);
     }
     p.cout[3 * pix] = o0;
     p.cout[3 * pix + 1] = o1;
@@ -129,10 +224,6 @@ __global__ void __launch_bounds__(THREADS) atrous_kernel(const AtrousParams p) {
     if constexpr (FIRST) {
         if (p.gout) p.gout[pix] = gp;
     }
-}
-
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
 }
 
 template <int T>
@@ -157,6 +248,35 @@ uint32_t lattice_from() {
     return 2u;
 }
 
+// Pass i of a frame: step 2^i on tiles of pitch g (lattice_from()), taps T = step / g points apart; the grid has
+// the lattice (lx, ly) in the low part of the block index: neighbouring workgroups read the same lines.
+struct Pass {
+    uint32_t step, pitch, T;
+    dim3 grid;
+};
+Pass pass_of(uint32_t i, uint32_t width, uint32_t rows, uint32_t lat) {
+    const uint32_t step = 1u << i, g = step >= lat ? step : 1u;
+    const uint32_t lw = (width + g - 1) / g, lh = (rows + g - 1) / g;
+    return {step, g, step / g, dim3(((lw + TW - 1) / TW) * g, ((lh + TH - 1) / TH) * g)};
+}
+
+// f(std::integral_constant<int, T>) for T = 1, 2, 4: the pass kernels' template argument
+template <class F>
+void with_T(uint32_t t, F&& f) {
+    if (t == 1) f(std::integral_constant<int, 1>());
+    else if (t == 2) f(std::integral_constant<int, 2>());
+    else f(std::integral_constant<int, 4>());
+}
+
+// (destructors: no exception leaves; a device that cannot be made current has nothing left to free)
+void free_on_device(int device, std::initializer_list<void*> ptrs) noexcept {
+    try {
+        DeviceGuard guard(device);
+        for (void* p : ptrs) (void)hipFree(p);
+    } catch (...) {
+    }
+}
+
 }  // namespace
 
 struct DenoiseScratch {
@@ -170,37 +290,22 @@ struct DenoiseScratch {
 
 void gpu_denoise_scratch_free(DenoiseScratch* s) {
     if (!s) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(s->device);
-    (void)hipFree(s->ping);
-    (void)hipFree(s->pong);
-    (void)hipFree(s->guides);
-    (void)hipSetDevice(prev);
+    free_on_device(s->device, {s->ping, s->pong, s->guides});
     delete s;
 }
 
 DenoiseScratch* gpu_denoise_scratch(DenoiseScratch* have, size_t pixels, int device, size_t rec_bytes) {
     if (have && have->device == device && have->pixels >= pixels && have->rec_bytes >= rec_bytes) return have;
     gpu_denoise_scratch_free(have);  // (hipFree waits for the device: no pass still reads the old buffers)
-    auto* s = new DenoiseScratch();
+    std::unique_ptr<DenoiseScratch, decltype(&gpu_denoise_scratch_free)> s(new DenoiseScratch(), gpu_denoise_scratch_free);
     s->device = device;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    try {
-        check(hipSetDevice(device), "hipSetDevice");
-        check(hipMalloc((void**)&s->ping, pixels * rec_bytes), "hipMalloc(denoise scratch)");
-        check(hipMalloc((void**)&s->pong, pixels * rec_bytes), "hipMalloc(denoise scratch)");
-        check(hipMalloc((void**)&s->guides, pixels * sizeof(float4)), "hipMalloc(denoise scratch)");
-        s->pixels = pixels;
-        s->rec_bytes = rec_bytes;
-    } catch (...) {
-        (void)hipSetDevice(prev);
-        gpu_denoise_scratch_free(s);
-        throw;
-    }
-    (void)hipSetDevice(prev);
-    return s;
+    DeviceGuard guard(device);
+    check(hipMalloc((void**)&s->ping, pixels * rec_bytes), "hipMalloc(denoise scratch)");
+    check(hipMalloc((void**)&s->pong, pixels * rec_bytes), "hipMalloc(denoise scratch)");
+    check(hipMalloc((void**)&s->guides, pixels * sizeof(float4)), "hipMalloc(denoise scratch)");
+    s->pixels = pixels;
+    s->rec_bytes = rec_bytes;
+    return s.release();
 }
 
 void gpu_denoise(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
@@ -209,45 +314,26 @@ void gpu_denoise(DenoiseScratch* s, const float* colour, const float* albedo, co
     const size_t pixels = (size_t)width * rows;
     if (!s || s->pixels < pixels || s->rec_bytes < 3 * sizeof(float)) throw std::runtime_error("denoise scratch too small");
     hipStream_t stream = (hipStream_t)stream_ptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    check(hipSetDevice(s->device), "hipSetDevice");
-    const double log2e = 1.4426950408889634;
+    DeviceGuard guard(s->device);
     const uint32_t lat = lattice_from();
     // a single pass in place would read the halo of pixels other workgroups have already replaced
     const bool alias = iterations == 1 && colour < out + pixels * 3 && out < colour + pixels * 3;
-    const float* src = colour;
+    auto p = frame_params<AtrousParams>(colour, albedo, normal, depth, width, rows, sigma_normal, sigma_depth, nullptr);
+    p.gin = s->guides;
     float* bufs[2] = {s->ping, s->pong};
     for (uint32_t i = 0; i < iterations; ++i) {
         const bool first = i == 0, last = i + 1 == iterations;
-        const uint32_t step = 1u << i, g = step >= lat ? step : 1u;
-        AtrousParams p{};
-        p.cin = src;
-        p.albedo = albedo;
-        p.normal = normal;
-        p.depth = depth;
-        p.gin = s->guides;
+        const Pass pass = pass_of(i, width, rows, lat);
         p.gout = last ? nullptr : s->guides;
         p.cout = last && !alias ? out : bufs[i & 1u];
-        p.width = width;
-        p.height = rows;
-        p.pitch = g;
-        const double sc = (double)sigma_color / (double)step;
-        p.kc = (float)(log2e / (sc * sc));
-        p.kn = (float)(log2e / ((double)sigma_normal * sigma_normal));
-        p.kz = (float)(log2e / ((double)sigma_depth * sigma_depth));
-        // lattice (lx, ly) in the low part of the block index: neighbouring workgroups read the same lines
-        const uint32_t lw = (width + g - 1) / g, lh = (rows + g - 1) / g;
-        const dim3 grid(((lw + TW - 1) / TW) * g, ((lh + TH - 1) / TH) * g);
-        if (step / g == 1) launch_pass<1>(p, first, last, grid, stream);
-        else if (step / g == 2) launch_pass<2>(p, first, last, grid, stream);
-        else launch_pass<4>(p, first, last, grid, stream);
-        src = p.cout;
+        p.pitch = pass.pitch;
+        const double sc = (double)sigma_color / (double)pass.step;
+        p.kc = (float)(LOG2E / (sc * sc));
+        with_T(pass.T, [&](auto T) { launch_pass<decltype(T)::value>(p, first, last, pass.grid, stream); });
+        p.colour = p.cout;
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && alias) e = hipMemcpyAsync(out, src, pixels * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream);
-    (void)hipSetDevice(prev);
-    check(e, "denoise launch");
+    check(hipGetLastError(), "denoise launch");
+    if (alias) check(hipMemcpyAsync(out, p.colour, pixels * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream), "denoise launch");
 }
 
 // ---- variance-guided filter: 7 x 7 moments kernel, then K passes over (colour, variance) records
@@ -256,22 +342,6 @@ namespace {
 constexpr int VR = 3;                                   // the moments window's radius
 constexpr int VW = TW + 2 * VR, VH = TH + 2 * VR;       // 38 x 14 slots
 constexpr int VPIX = VW * VH;
-
-struct VgParams {
-    const float* colour;  // moments kernel: the caller's colour
-    const float* albedo;  // moments kernel (demodulation) and LAST (remodulation)
-    const float* normal;  // moments kernel
-    const float* depth;   // moments kernel
-    const float4* rin;    // passes: (D_i.rgb, Var_i)
-    const float4* gin;    // passes: the guide records (normal.xyz, depth) the moments kernel packed
-    float4* rout;         // moments kernel: (D_0, Var_0); passes but LAST: (D_{i+1}, Var_{i+1})
-    float4* gout;         // moments kernel
-    float* cout;          // LAST: the caller's output, 3 f32 per pixel
-    float* vout;          // LAST: the caller's variance buffer, 1 f32 per pixel, or null
-    uint32_t width, height;
-    uint32_t pitch;       // as AtrousParams
-    float sigma_l, kn, kz;  // sigma_l, log2(e) / sigma_n^2, log2(e) / sigma_z^2
-};
 
 __device__ __forceinline__ float lum(float r, float g, float b) {
     return fmaf(0.2126f, r, fmaf(0.7152f, g, 0.0722f * b));
@@ -290,12 +360,11 @@ __device__ __forceinline__ void vg_stage(const VgParams& p, float4* sg, float* s
         const int x = tx0 - VR + u, y = ty0 - VR + v;
         float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         float l = 0.0f;
-        if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
+        if (in_range(x, W) && in_range(y, H)) {
             const size_t a = (size_t)y * p.width + (size_t)x;
-            r = make_float4(p.normal[3 * a], p.normal[3 * a + 1], p.normal[3 * a + 2], p.depth[a]);
-            l = lum(p.colour[3 * a] / fmaxf(p.albedo[3 * a], ALBEDO_FLOOR),
-                    p.colour[3 * a + 1] / fmaxf(p.albedo[3 * a + 1], ALBEDO_FLOOR),
-                    p.colour[3 * a + 2] / fmaxf(p.albedo[3 * a + 2], ALBEDO_FLOOR));
+            r = load_guide(p, a);
+            l = lum(demodulate(p.colour, p.albedo, 3 * a), demodulate(p.colour, p.albedo, 3 * a + 1),
+                    demodulate(p.colour, p.albedo, 3 * a + 2));
         }
         sg[q] = r;
         sl[q] = l;
@@ -310,10 +379,10 @@ __device__ __forceinline__ float vg_var0(const VgParams& p, const float4* sg, co
     float sw = 0.0f, s1 = 0.0f, s2 = 0.0f;
 #pragma unroll 1
     for (int dy = -VR; dy <= VR; ++dy) {
-        const bool oky = (unsigned)(py + dy) < (unsigned)H;
+        const bool oky = in_range(py + dy, H);
 #pragma unroll
         for (int dx = -VR; dx <= VR; ++dx) {
-            const bool ok = oky && (unsigned)(px + dx) < (unsigned)W;
+            const bool ok = oky && in_range(px + dx, W);
             const int q = cq + dy * VW + dx;
             const float4 gq = sg[q];
             const float d = sl[q] - lp;
@@ -346,9 +415,8 @@ __global__ void __launch_bounds__(THREADS) vg_moments_kernel(const VgParams p) {
     const size_t pix = (size_t)py * p.width + (size_t)px;
     // the lane's own D_0 again from memory (the lines the staging loop just read): the same divisions,
     // so the luminance of this record is the staged one
-    p.rout[pix] = make_float4(p.colour[3 * pix] / fmaxf(p.albedo[3 * pix], ALBEDO_FLOOR),
-                              p.colour[3 * pix + 1] / fmaxf(p.albedo[3 * pix + 1], ALBEDO_FLOOR),
-                              p.colour[3 * pix + 2] / fmaxf(p.albedo[3 * pix + 2], ALBEDO_FLOOR), var0);
+    p.rout[pix] = make_float4(demodulate(p.colour, p.albedo, 3 * pix), demodulate(p.colour, p.albedo, 3 * pix + 1),
+                              demodulate(p.colour, p.albedo, 3 * pix + 2), var0);
     p.gout[pix] = sg[cq];
 }
 
@@ -366,67 +434,58 @@ __global__ void __launch_bounds__(THREADS) vg_moments_kernel(const VgParams p) {
 // lattices' workgroups (adjacent block indices) stage.
 template <int T, bool LAST>
 __global__ void __launch_bounds__(THREADS) vg_atrous_kernel(const VgParams p) {
-    constexpr int RW = TW + 4 * T, RH = TH + 4 * T, NPIX = RW * RH;
-    __shared__ float4 sr[NPIX];
-    __shared__ float4 sg[NPIX];
-    const int g = (int)p.pitch, W = (int)p.width, H = (int)p.height;
-    const int lx = (int)(blockIdx.x % p.pitch), ly = (int)(blockIdx.y % p.pitch);
-    const int tx0 = (int)(blockIdx.x / p.pitch) * TW, ty0 = (int)(blockIdx.y / p.pitch) * TH;  // lattice coordinates
-    if (lx + tx0 * g >= W || ly + ty0 * g >= H) return;  // (uniform) a tile past the end of a short lattice
+    using Tile = LatticeTile<T>;
+    __shared__ float4 sr[Tile::NPIX];
+    __shared__ float4 sg[Tile::NPIX];
+    const Tile t(p);
+    if (t.x0() >= t.W || t.y0() >= t.H) return;
     const int tid = (int)threadIdx.x;
-    const int tx = tid % TW, ty = tid / TW;
-    const int px = lx + (tx0 + tx) * g, py = ly + (ty0 + ty) * g;
-    const bool mine = px < W && py < H;
-    constexpr float g3[3] = {0.25f, 0.5f, 0.25f};
+    const typename Tile::Lane me(t, tid);
+    const bool mine = me.px < t.W && me.py < t.H;
     float pv = 0.0f, pk = 0.0f;
     if (mine) {
 #pragma unroll
         for (int dy = -1; dy <= 1; ++dy) {
 #pragma unroll
             for (int dx = -1; dx <= 1; ++dx) {
-                const int x = px + dx, y = py + dy;
-                if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
-                    pv += g3[dx + 1] * g3[dy + 1] * p.rin[(size_t)y * p.width + (size_t)x].w;
-                    pk += g3[dx + 1] * g3[dy + 1];
+                const int x = me.px + dx, y = me.py + dy;
+                if (in_range(x, t.W) && in_range(y, t.H)) {
+                    pv += g3(dx + 1) * g3(dy + 1) * p.rin[(size_t)y * p.width + (size_t)x].w;
+                    pk += g3(dx + 1) * g3(dy + 1);
                 }
             }
         }
     }
-    // region slot (u, v) -> pixel (lx + (tx0 - 2 T + u) g, ly + (ty0 - 2 T + v) g)
-    for (int q = tid; q < NPIX; q += THREADS) {
-        const int v = q / RW, u = q - v * RW;
-        const int x = lx + (tx0 - 2 * T + u) * g, y = ly + (ty0 - 2 * T + v) * g;
+    for (int q = tid; q < Tile::NPIX; q += THREADS) {
+        const int2 xy = t.slot_pixel(q);
         float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f), k = r;
-        if ((unsigned)x < (unsigned)W && (unsigned)y < (unsigned)H) {
-            const size_t a = (size_t)y * p.width + (size_t)x;
-            r = p.rin[a];
-            k = p.gin[a];
+        if (in_range(xy.x, t.W) && in_range(xy.y, t.H)) {
+            r = p.rin[t.index(xy)];
+            k = p.gin[t.index(xy)];
         }
         sr[q] = r;
         sg[q] = k;
     }
     __syncthreads();
     if (!mine) return;
-    const int s = T * g;
-    const int cq = (ty + 2 * T) * RW + tx + 2 * T;
+    const int cq = me.cq;
     const float4 gp = sg[cq], rp = sr[cq];
     const float lp = lum(rp.x, rp.y, rp.z);
     // log2(e) / (sigma_l sigma(p) + 1e-6): the centre tap's own weight 1/4 keeps pk >= 1/4
-    const float kl = 1.4426950408889634f / (p.sigma_l * sqrtf(pv / pk) + 1e-6f);
-    constexpr float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    const float kl = (float)LOG2E / (p.sigma_l * sqrtf(pv / pk) + 1e-6f);
     float sw = 0.0f, a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, av = 0.0f;
 #pragma unroll
     for (int dy = -2; dy <= 2; ++dy) {
-        const bool oky = (unsigned)(py + dy * s) < (unsigned)H;
+        const bool oky = me.row_ok(dy);
 #pragma unroll
         for (int dx = -2; dx <= 2; ++dx) {
-            const bool ok = oky && (unsigned)(px + dx * s) < (unsigned)W;
-            const int q = cq + dy * T * RW + dx * T;
+            const bool ok = oky && me.col_ok(dx);
+            const int q = me.tap(dx, dy);
             const float4 gq = sg[q], rq = sr[q];
             const float dl = fabsf(lp - lum(rq.x, rq.y, rq.z));
             const float n0 = gp.x - gq.x, n1 = gp.y - gq.y, n2 = gp.z - gq.z, dz = gp.w - gq.w;
             const float e = dl * kl + (n0 * n0 + n1 * n1 + n2 * n2) * p.kn + dz * dz * p.kz;
-            const float w = ok ? hk[dx + 2] * hk[dy + 2] * __builtin_amdgcn_exp2f(-e) : 0.0f;
+            const float w = ok ? h5(dx + 2) * h5(dy + 2) * __builtin_amdgcn_exp2f(-e) : 0.0f;
             sw += w;
             a0 += w * rq.x;
             a1 += w * rq.y;
@@ -437,11 +496,11 @@ __global__ void __launch_bounds__(THREADS) vg_atrous_kernel(const VgParams p) {
     // (the centre tap has e = 0: sw >= 9/64)
     float o0 = a0 / sw, o1 = a1 / sw, o2 = a2 / sw;
     const float ov = av / (sw * sw);
-    const size_t pix = (size_t)py * p.width + (size_t)px;
+    const size_t pix = me.pix();
     if constexpr (LAST) {
-        p.cout[3 * pix] = o0 * fmaxf(p.albedo[3 * pix], ALBEDO_FLOOR);
-        p.cout[3 * pix + 1] = o1 * fmaxf(p.albedo[3 * pix + 1], ALBEDO_FLOOR);
-        p.cout[3 * pix + 2] = o2 * fmaxf(p.albedo[3 * pix + 2], ALBEDO_FLOOR);
+        p.cout[3 * pix] = remodulate(o0, p.albedo, 3 * pix);
+        p.cout[3 * pix + 1] = remodulate(o1, p.albedo, 3 * pix + 1);
+        p.cout[3 * pix + 2] = remodulate(o2, p.albedo, 3 * pix + 2);
         if (p.vout) p.vout[pix] = ov;
     } else {
         p.rout[pix] = make_float4(o0, o1, o2, ov);
@@ -459,36 +518,12 @@ void launch_vg_pass(const VgParams& p, bool last, dim3 grid, hipStream_t stream)
 void enqueue_vg_passes(VgParams p, uint32_t iterations, float4* const* chain, hipStream_t stream) {
     const uint32_t lat = lattice_from();
     for (uint32_t i = 0; i < iterations; ++i) {
-        const uint32_t step = 1u << i, g = step >= lat ? step : 1u;
+        const Pass pass = pass_of(i, p.width, p.height, lat);
         p.rin = chain[i];
         p.rout = chain[i + 1];
-        p.pitch = g;
-        const uint32_t lw = (p.width + g - 1) / g, lh = (p.height + g - 1) / g;
-        const dim3 grid(((lw + TW - 1) / TW) * g, ((lh + TH - 1) / TH) * g);
-        if (step / g == 1) launch_vg_pass<1>(p, i + 1 == iterations, grid, stream);
-        else if (step / g == 2) launch_vg_pass<2>(p, i + 1 == iterations, grid, stream);
-        else launch_vg_pass<4>(p, i + 1 == iterations, grid, stream);
+        p.pitch = pass.pitch;
+        with_T(pass.T, [&](auto T) { launch_vg_pass<decltype(T)::value>(p, i + 1 == iterations, pass.grid, stream); });
     }
-}
-
-// (the fields every vg launch shares)
-VgParams vg_params(const float* colour, const float* albedo, const float* normal, const float* depth, uint32_t width,
-                   uint32_t rows, float sigma_luminance, float sigma_normal, float sigma_depth, float* out,
-                   float* out_variance) {
-    const double log2e = 1.4426950408889634;
-    VgParams p{};
-    p.colour = colour;
-    p.albedo = albedo;
-    p.normal = normal;
-    p.depth = depth;
-    p.cout = out;
-    p.vout = out_variance;
-    p.width = width;
-    p.height = rows;
-    p.sigma_l = sigma_luminance;
-    p.kn = (float)(log2e / ((double)sigma_normal * sigma_normal));
-    p.kz = (float)(log2e / ((double)sigma_depth * sigma_depth));
-    return p;
 }
 
 }  // namespace
@@ -501,22 +536,19 @@ void gpu_denoise_vg(DenoiseScratch* s, const float* colour, const float* albedo,
     const size_t pixels = (size_t)width * rows;
     if (!s || s->pixels < pixels || s->rec_bytes < sizeof(float4)) throw std::runtime_error("denoise scratch too small");
     hipStream_t stream = (hipStream_t)stream_ptr;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    check(hipSetDevice(s->device), "hipSetDevice");
+    DeviceGuard guard(s->device);
     float4* const b0 = (float4*)s->ping;
     float4* const b1 = (float4*)s->pong;
     float4* const chain[6] = {b0, b1, b0, b1, b0, b1};
-    VgParams p = vg_params(colour, albedo, normal, depth, width, rows, sigma_luminance, sigma_normal, sigma_depth, out,
-                           out_variance);
+    auto p = frame_params<VgParams>(colour, albedo, normal, depth, width, rows, sigma_normal, sigma_depth, out);
+    p.vout = out_variance;
+    p.sigma_l = sigma_luminance;
+    p.rout = b0;
     p.gin = s->guides;
     p.gout = s->guides;
-    p.rout = b0;
     hipLaunchKernelGGL(vg_moments_kernel, dim3((width + TW - 1) / TW, (rows + TH - 1) / TH), dim3(THREADS), 0, stream, p);
     enqueue_vg_passes(p, iterations, chain, stream);
-    const hipError_t e = hipGetLastError();
-    (void)hipSetDevice(prev);
-    check(e, "denoise_vg launch");
+    check(hipGetLastError(), "denoise_vg launch");
 }
 
 // ---- temporal accumulation (SVGF's temporal half): one kernel in the moments kernel's place, then
@@ -556,23 +588,24 @@ struct TemporalParams {
 __global__ void __launch_bounds__(THREADS) temporal_kernel(const TemporalParams p) {
     __shared__ float4 sg[VPIX];
     __shared__ float sl[VPIX];
-    const int W = (int)p.v.width, H = (int)p.v.height;
+    const VgParams& f = p.v;
+    const int W = (int)f.width, H = (int)f.height;
     const int tx0 = (int)blockIdx.x * TW, ty0 = (int)blockIdx.y * TH;
     const int tid = (int)threadIdx.x;
     const int tx = tid % TW, ty = tid / TW;
     const int px = tx0 + tx, py = ty0 + ty;
     const bool mine = px < W && py < H;
-    const size_t pix = mine ? (size_t)py * p.v.width + (size_t)px : 0;
+    const size_t pix = mine ? (size_t)py * f.width + (size_t)px : 0;
     const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float4 tg[4] = {zero, zero, zero, zero}, th[4] = {zero, zero, zero, zero}, tm[4] = {zero, zero, zero, zero};
     float4 gp = zero;
     float d0 = 0.0f, d1 = 0.0f, d2 = 0.0f, fx = 0.0f, fy = 0.0f, zr = 0.0f;
     bool reproj = false;
     if (mine) {
-        gp = make_float4(p.v.normal[3 * pix], p.v.normal[3 * pix + 1], p.v.normal[3 * pix + 2], p.v.depth[pix]);
-        d0 = p.v.colour[3 * pix] / fmaxf(p.v.albedo[3 * pix], ALBEDO_FLOOR);
-        d1 = p.v.colour[3 * pix + 1] / fmaxf(p.v.albedo[3 * pix + 1], ALBEDO_FLOOR);
-        d2 = p.v.colour[3 * pix + 2] / fmaxf(p.v.albedo[3 * pix + 2], ALBEDO_FLOOR);
+        gp = load_guide(f, pix);
+        d0 = demodulate(f.colour, f.albedo, 3 * pix);
+        d1 = demodulate(f.colour, f.albedo, 3 * pix + 1);
+        d2 = demodulate(f.colour, f.albedo, 3 * pix + 2);
         if (p.have_prev && gp.w > 0.0f) {
             const float x = (float)px, y = (float)py;
             const float r0 = fmaf(y, p.dv[0], fmaf(x, p.du[0], p.c0[0]));
@@ -598,8 +631,8 @@ __global__ void __launch_bounds__(THREADS) temporal_kernel(const TemporalParams 
                 for (int j = 0; j < 2; ++j) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
-                        if ((unsigned)(ix + i) < (unsigned)W && (unsigned)(iy + j) < (unsigned)H) {
-                            const size_t a = (size_t)(iy + j) * p.v.width + (size_t)(ix + i);
+                        if (in_range(ix + i, W) && in_range(iy + j, H)) {
+                            const size_t a = (size_t)(iy + j) * f.width + (size_t)(ix + i);
                             tg[2 * j + i] = p.pg[a];
                             th[2 * j + i] = p.ph[a];
                             tm[2 * j + i] = p.pm[a];
@@ -609,7 +642,7 @@ __global__ void __launch_bounds__(THREADS) temporal_kernel(const TemporalParams 
             }
         }
     }
-    vg_stage(p.v, sg, sl, tx0, ty0, tid);
+    vg_stage(f, sg, sl, tx0, ty0, tid);
     __syncthreads();
     if (!mine) return;
     const int cq = (ty + VR) * VW + tx + VR;
@@ -648,12 +681,12 @@ __global__ void __launch_bounds__(THREADS) temporal_kernel(const TemporalParams 
     }
     float var = fmaxf(0.0f, m2 - m1 * m1);
     if (__ballot(n < 4.0f) != 0ull) {  // wave-uniform
-        const float var0 = vg_var0(p.v, sg, sl, cq, px, py);
+        const float var0 = vg_var0(f, sg, sl, cq, px, py);
         if (n < 4.0f) var = var0 / n;
     }
     p.v.rout[pix] = make_float4(i0, i1, i2, var);
     p.mout[pix] = make_float4(m1, m2, n, 0.0f);
-    p.v.gout[pix] = gp;
+    f.gout[pix] = gp;
 }
 
 // 3 x 3 inverse in f64 (columns a, b, c), row-major; false when the determinant is below 1e-12 of the
@@ -698,15 +731,9 @@ History* gpu_history_new(uint32_t width, uint32_t rows) {
 
 void gpu_history_free(History* h) {
     if (!h) return;
-    if (h->device >= 0) {
-        int prev = 0;
-        (void)hipGetDevice(&prev);
-        (void)hipSetDevice(h->device);
-        for (void* b : {(void*)h->guides[0], (void*)h->guides[1], (void*)h->moments[0], (void*)h->moments[1],
-                        (void*)h->hist, (void*)h->work[0], (void*)h->work[1], (void*)h->io})
-            (void)hipFree(b);
-        (void)hipSetDevice(prev);
-    }
+    if (h->device >= 0)
+        free_on_device(h->device, {h->guides[0], h->guides[1], h->moments[0], h->moments[1], h->hist, h->work[0],
+                                   h->work[1], h->io});
     delete h;
 }
 
@@ -736,19 +763,9 @@ void history_alloc(History* h, int device) {
 }  // namespace
 
 float* gpu_history_io(History* h, int device) {
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    check(hipSetDevice(device), "hipSetDevice");
-    hipError_t e = hipSuccess;
-    try {
-        history_alloc(h, device);
-        if (!h->io) e = hipMalloc((void**)&h->io, (size_t)h->width * h->rows * 11 * sizeof(float));
-    } catch (...) {
-        (void)hipSetDevice(prev);
-        throw;
-    }
-    (void)hipSetDevice(prev);
-    check(e, "hipMalloc(history staging)");
+    DeviceGuard guard(device);
+    history_alloc(h, device);
+    if (!h->io) check(hipMalloc((void**)&h->io, (size_t)h->width * h->rows * 11 * sizeof(float)), "hipMalloc(history staging)");
     return h->io;
 }
 
@@ -788,18 +805,12 @@ void gpu_denoise_temporal(History* h, int device, const TemporalCamera& cam, con
         t.du[i] = (float)cam.du[i];
         t.dv[i] = (float)cam.dv[i];
     }
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    check(hipSetDevice(device), "hipSetDevice");
-    try {
-        history_alloc(h, device);
-    } catch (...) {
-        (void)hipSetDevice(prev);
-        throw;
-    }
+    DeviceGuard guard(device);
+    history_alloc(h, device);
     const uint32_t cur = h->parity ^ 1u;
-    t.v = vg_params(colour, albedo, normal, depth, h->width, h->rows, sigma_luminance, sigma_normal, sigma_depth, out,
-                    out_variance);
+    t.v = frame_params<VgParams>(colour, albedo, normal, depth, h->width, h->rows, sigma_normal, sigma_depth, out);
+    t.v.vout = out_variance;
+    t.v.sigma_l = sigma_luminance;
     t.v.rout = h->work[0];
     t.v.gout = h->guides[cur];
     t.v.gin = h->guides[cur];
@@ -815,9 +826,7 @@ void gpu_denoise_temporal(History* h, int device, const TemporalCamera& cam, con
                        stream, t);
     float4* const chain[6] = {h->work[0], h->hist, h->work[0], h->work[1], h->work[0], h->work[1]};
     enqueue_vg_passes(t.v, iterations, chain, stream);
-    const hipError_t e = hipGetLastError();
-    (void)hipSetDevice(prev);
-    check(e, "denoise_temporal launch");
+    check(hipGetLastError(), "denoise_temporal launch");
     h->parity = cur;
     h->cam = cam;
     h->frames += 1;
@@ -829,13 +838,9 @@ void gpu_history_read(History* h, float* moments, float* length) {
     if (!h->written) throw std::invalid_argument("history_read: no frame yet");
     const size_t n = (size_t)h->width * h->rows;
     std::vector<float4> rec(n);
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    check(hipSetDevice(h->device), "hipSetDevice");
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(rec.data(), h->moments[h->parity], n * sizeof(float4), hipMemcpyDeviceToHost);
-    (void)hipSetDevice(prev);
-    check(e, "history_read");
+    DeviceGuard guard(h->device);
+    check(hipDeviceSynchronize(), "history_read");
+    check(hipMemcpy(rec.data(), h->moments[h->parity], n * sizeof(float4), hipMemcpyDeviceToHost), "history_read");
     for (size_t i = 0; i < n; ++i) {
         if (moments) moments[2 * i] = rec[i].x, moments[2 * i + 1] = rec[i].y;
         if (length) length[i] = rec[i].z;

@@ -49,14 +49,11 @@
 #include <vector>
 
 #include "gpu.hpp"
+#include "hip_util.hpp"
 #include "nrt.h"
 
 namespace nrt {
 namespace {
-
-void hcheck(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
-}
 
 struct Rccl {
     bool ok = false;
@@ -102,17 +99,6 @@ void ncheck(ncclResult_t r, const char* what) {
     if (r != ncclSuccess)
         throw std::runtime_error(std::string("HIP error in RCCL ") + what + ": " + rccl().error_string(r));
 }
-
-struct Guard {  // the caller's current device is restored (render.hip DeviceGuard)
-    int prev = -1;
-    explicit Guard(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (d != prev) hcheck(hipSetDevice(d), "hipSetDevice");
-    }
-    ~Guard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 // Frame row y <- shard y % N, its row y / N.  One workgroup per frame row, 16-B moves when the
 // row is a whole number of them (W x 3 floats: W % 4 == 0), else 4-B moves.
@@ -188,13 +174,13 @@ namespace {
 
 void free_buffers(MultiRender* m) {
     for (int d = 0; d < m->n; ++d) {
-        Guard g(m->dev_of(d));
+        DeviceGuard g(m->dev_of(d));
         for (int s = 0; s < m->pipe; ++s) {
             if (m->dev[(size_t)d].rows[s]) (void)hipFree(m->dev[(size_t)d].rows[s]);
             m->dev[(size_t)d].rows[s] = nullptr;
         }
     }
-    Guard g(m->first);
+    DeviceGuard g(m->first);
     for (int s = 0; s < m->pipe; ++s) {
         if (m->staging[s]) (void)hipFree(m->staging[s]);
         m->staging[s] = nullptr;
@@ -208,7 +194,7 @@ void free_buffers(MultiRender* m) {
 // streams) the last gather event of every buffer set
 void sync_all(MultiRender* m) {
     for (int d = 0; d < m->n; ++d) {
-        Guard g(m->dev_of(d));
+        DeviceGuard g(m->dev_of(d));
         const MultiRender::Dev& x = m->dev[(size_t)d];
         for (int s = 0; s < m->nrs; ++s)
             if (x.rs[s]) (void)hipStreamSynchronize(x.rs[s]);
@@ -217,7 +203,7 @@ void sync_all(MultiRender* m) {
         if (x.cs) (void)hipStreamSynchronize(x.cs);
     }
     if (m->host_stream) {
-        Guard g(m->first);
+        DeviceGuard g(m->first);
         (void)hipStreamSynchronize(m->host_stream);
     }
 }
@@ -229,15 +215,15 @@ void ensure_buffers(MultiRender* m, uint32_t W, uint32_t H) {
     const uint32_t rows_max = (H + (uint32_t)m->n - 1) / (uint32_t)m->n;
     const size_t shard = (size_t)rows_max * W * 3 * sizeof(float);
     for (int d = 0; d < m->n; ++d) {
-        Guard g(m->dev_of(d));
+        DeviceGuard g(m->dev_of(d));
         for (int s = 0; s < m->pipe; ++s) {
-            hcheck(hipMalloc((void**)&m->dev[(size_t)d].rows[s], shard), "hipMalloc(row shard)");
-            hcheck(hipMemset(m->dev[(size_t)d].rows[s], 0, shard), "hipMemset(row shard)");  // rows past a short shard
+            check(hipMalloc((void**)&m->dev[(size_t)d].rows[s], shard), "hipMalloc(row shard)");
+            check(hipMemset(m->dev[(size_t)d].rows[s], 0, shard), "hipMemset(row shard)");  // rows past a short shard
         }
-        hcheck(hipDeviceSynchronize(), "hipMemset(row shard)");  // (the render streams do not block on it)
+        check(hipDeviceSynchronize(), "hipMemset(row shard)");  // (the render streams do not block on it)
     }
-    Guard g(m->first);
-    for (int s = 0; s < m->pipe; ++s) hcheck(hipMalloc((void**)&m->staging[s], shard * (size_t)m->n), "hipMalloc(staging)");
+    DeviceGuard g(m->first);
+    for (int s = 0; s < m->pipe; ++s) check(hipMalloc((void**)&m->staging[s], shard * (size_t)m->n), "hipMalloc(staging)");
     m->W = W;
     m->H = H;
     m->rows_max = rows_max;
@@ -267,25 +253,25 @@ MultiRender* gpu_multi_create(const std::vector<DeviceScene*>& scenes, bool loop
             devlist.push_back(m->dev_of(d));
         }
         for (int d = 0; d < m->n; ++d) {
-            Guard g(m->dev_of(d));
+            DeviceGuard g(m->dev_of(d));
             MultiRender::Dev& x = m->dev[(size_t)d];
             for (int s = 0; s < m->nrs; ++s)
-                hcheck(hipStreamCreateWithFlags(&x.rs[s], hipStreamNonBlocking), "hipStreamCreate");
+                check(hipStreamCreateWithFlags(&x.rs[s], hipStreamNonBlocking), "hipStreamCreate");
             for (int s = 0; s < m->pipe; ++s) {
-                hcheck(hipEventCreateWithFlags(&x.rendered[s], hipEventDisableTiming), "hipEventCreate");
-                hcheck(hipEventCreateWithFlags(&x.gathered[s], hipEventDisableTiming), "hipEventCreate");
-                hcheck(hipEventCreate(&x.t0[s]), "hipEventCreate");
-                hcheck(hipEventCreate(&x.t1[s]), "hipEventCreate");
+                check(hipEventCreateWithFlags(&x.rendered[s], hipEventDisableTiming), "hipEventCreate");
+                check(hipEventCreateWithFlags(&x.gathered[s], hipEventDisableTiming), "hipEventCreate");
+                check(hipEventCreate(&x.t0[s]), "hipEventCreate");
+                check(hipEventCreate(&x.t1[s]), "hipEventCreate");
             }
-            if (d > 0) hcheck(hipStreamCreateWithFlags(&x.cs, hipStreamNonBlocking), "hipStreamCreate");
+            if (d > 0) check(hipStreamCreateWithFlags(&x.cs, hipStreamNonBlocking), "hipStreamCreate");
         }
         {
-            Guard g(m->first);
-            hcheck(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking), "hipStreamCreate");
-            hcheck(hipEventCreate(&m->w0), "hipEventCreate");
+            DeviceGuard g(m->first);
+            check(hipStreamCreateWithFlags(&m->host_stream, hipStreamNonBlocking), "hipStreamCreate");
+            check(hipEventCreate(&m->w0), "hipEventCreate");
             for (int s = 0; s < m->pipe; ++s) {
-                hcheck(hipEventCreate(&m->g0[s]), "hipEventCreate");
-                hcheck(hipEventCreate(&m->g1[s]), "hipEventCreate");
+                check(hipEventCreate(&m->g0[s]), "hipEventCreate");
+                check(hipEventCreate(&m->g1[s]), "hipEventCreate");
             }
         }
         if (need_rccl) {
@@ -319,7 +305,7 @@ void gpu_multi_free(MultiRender* m) {
         if (c) (void)rccl().destroy(c);
     free_buffers(m);
     for (int d = 0; d < m->n; ++d) {
-        Guard g(m->dev_of(d));
+        DeviceGuard g(m->dev_of(d));
         MultiRender::Dev& x = m->dev[(size_t)d];
         for (int s = 0; s < m->pipe; ++s) {
             for (hipEvent_t e : {x.rendered[s], x.gathered[s], x.t0[s], x.t1[s]})
@@ -330,7 +316,7 @@ void gpu_multi_free(MultiRender* m) {
         if (x.cs) (void)hipStreamDestroy(x.cs);
     }
     {
-        Guard g(m->first);
+        DeviceGuard g(m->first);
         for (int s = 0; s < m->pipe; ++s)
             for (hipEvent_t e : {m->g0[s], m->g1[s]})
                 if (e) (void)hipEventDestroy(e);
@@ -356,11 +342,11 @@ void enqueue(MultiRender* m, const RenderParams& p0, uint32_t precision, uint32_
     const int rsi = (int)(m->frames % (uint64_t)m->nrs);   // render stream
     const uint32_t N = (uint32_t)m->n;
     for (int d = 0; d < m->n; ++d) {
-        Guard g(m->dev_of(d));
+        DeviceGuard g(m->dev_of(d));
         MultiRender::Dev& x = m->dev[(size_t)d];
         hipStream_t rs = x.rs[rsi];
         // rows[s] is free once the gather of frame k - pipe has read it
-        hcheck(hipStreamWaitEvent(rs, x.gathered[s], 0), "hipStreamWaitEvent");
+        check(hipStreamWaitEvent(rs, x.gathered[s], 0), "hipStreamWaitEvent");
         RenderParams q = p0;
         q.row_offset = (uint32_t)d;
         q.row_stride = N;
@@ -368,34 +354,34 @@ void enqueue(MultiRender* m, const RenderParams& p0, uint32_t precision, uint32_
         q.pixel_begin = 0;
         q.pixel_end = q.rows * q.width;
         q.out = x.rows[s];
-        hcheck(hipEventRecord(x.t0[s], rs), "hipEventRecord");
+        check(hipEventRecord(x.t0[s], rs), "hipEventRecord");
         if (d == 0) {
             if (!m->w_armed) {
-                hcheck(hipEventRecord(m->w0, rs), "hipEventRecord");
+                check(hipEventRecord(m->w0, rs), "hipEventRecord");
                 m->w_armed = true;
                 m->w_frames = 0;
             }
             ++m->w_frames;
         }
         if (q.rows) gpu_launch_render(m->scenes[(size_t)d], q, precision, rng, trace, rs);
-        hcheck(hipEventRecord(x.t1[s], rs), "hipEventRecord");
-        hcheck(hipEventRecord(x.rendered[s], rs), "hipEventRecord");
+        check(hipEventRecord(x.t1[s], rs), "hipEventRecord");
+        check(hipEventRecord(x.rendered[s], rs), "hipEventRecord");
         hipStream_t cs = d == 0 ? stream : x.cs;
-        hcheck(hipStreamWaitEvent(cs, x.rendered[s], 0), "hipStreamWaitEvent");
+        check(hipStreamWaitEvent(cs, x.rendered[s], 0), "hipStreamWaitEvent");
         // device 0's gathers run on the callers' streams: one that differs from the last frame's must
         // not start this gather before the previous one (RCCL's per-communicator order)
         if (d == 0 && m->last >= 0)
-            hcheck(hipStreamWaitEvent(cs, x.gathered[m->last], 0), "hipStreamWaitEvent");
+            check(hipStreamWaitEvent(cs, x.gathered[m->last], 0), "hipStreamWaitEvent");
     }
     {
-        Guard g(m->first);
-        hcheck(hipEventRecord(m->g0[s], stream), "hipEventRecord");
+        DeviceGuard g(m->first);
+        check(hipEventRecord(m->g0[s], stream), "hipEventRecord");
     }
     const size_t count = (size_t)m->rows_max * m->W * 3;
     if (m->loopback || m->n == 1) {  // shard d's "gather": its rows into staging slot d, on its comm stream
         for (int d = 0; d < m->n; ++d) {
-            Guard g(m->first);
-            hcheck(hipMemcpyAsync(m->staging[s] + (size_t)d * count, m->dev[(size_t)d].rows[s], count * sizeof(float),
+            DeviceGuard g(m->first);
+            check(hipMemcpyAsync(m->staging[s] + (size_t)d * count, m->dev[(size_t)d].rows[s], count * sizeof(float),
                                   hipMemcpyDeviceToDevice, d == 0 ? stream : m->dev[(size_t)d].cs),
                    "hipMemcpyAsync(loopback gather)");
         }
@@ -403,7 +389,7 @@ void enqueue(MultiRender* m, const RenderParams& p0, uint32_t precision, uint32_
         ncheck(r.group_start(), "ncclGroupStart");
         ncclResult_t gr = ncclSuccess;
         for (int d = 0; d < m->n && gr == ncclSuccess; ++d) {
-            Guard g(m->dev_of(d));  // (RCCL's group launch reads the current device)
+            DeviceGuard g(m->dev_of(d));  // (RCCL's group launch reads the current device)
             gr = r.gather(m->dev[(size_t)d].rows[s], d == 0 ? m->staging[s] : nullptr, count, ncclFloat32, 0,
                           m->comms[(size_t)d], d == 0 ? stream : m->dev[(size_t)d].cs);
         }
@@ -412,20 +398,20 @@ void enqueue(MultiRender* m, const RenderParams& p0, uint32_t precision, uint32_
         ncheck(er, "ncclGroupEnd");
     }
     for (int d = 0; d < m->n; ++d) {
-        Guard g(m->dev_of(d));
-        hcheck(hipEventRecord(m->dev[(size_t)d].gathered[s], d == 0 ? stream : m->dev[(size_t)d].cs),
+        DeviceGuard g(m->dev_of(d));
+        check(hipEventRecord(m->dev[(size_t)d].gathered[s], d == 0 ? stream : m->dev[(size_t)d].cs),
                "hipEventRecord");
     }
-    Guard g(m->first);
+    DeviceGuard g(m->first);
     // RCCL's root completes its gather once every shard has arrived; the loopback copies of the other
     // shards ran on their own comm streams
     if (m->loopback)
         for (int d = 1; d < m->n; ++d)
-            hcheck(hipStreamWaitEvent(stream, m->dev[(size_t)d].gathered[s], 0), "hipStreamWaitEvent");
+            check(hipStreamWaitEvent(stream, m->dev[(size_t)d].gathered[s], 0), "hipStreamWaitEvent");
     hipLaunchKernelGGL(unpermute_rows, dim3(m->H), dim3(256), 0, stream, (const float*)m->staging[s], out, N,
                        m->rows_max, m->W * 3u);
-    hcheck(hipGetLastError(), "un-permute launch");
-    hcheck(hipEventRecord(m->g1[s], stream), "hipEventRecord");
+    check(hipGetLastError(), "un-permute launch");
+    check(hipEventRecord(m->g1[s], stream), "hipEventRecord");
     m->last = s;
     ++m->frames;
 }
@@ -434,7 +420,7 @@ void enqueue(MultiRender* m, const RenderParams& p0, uint32_t precision, uint32_
 void check_stream(const MultiRender* m, hipStream_t stream) {
     if (!stream) return;
     hipDevice_t d = -1;
-    hcheck(hipStreamGetDevice(stream, &d), "hipStreamGetDevice");
+    check(hipStreamGetDevice(stream, &d), "hipStreamGetDevice");
     if ((int)d != m->first)
         throw std::invalid_argument("gpus >= 1: hip_stream belongs to device " + std::to_string((int)d) +
                                     ", the frame to device " + std::to_string(m->first) +
@@ -455,11 +441,11 @@ void gpu_multi_render_host(MultiRender* m, const RenderParams& p, uint32_t preci
     std::lock_guard<std::mutex> lock(m->mu);
     ensure_buffers(m, p.width, p.height);
     const size_t bytes = (size_t)p.width * p.height * 3 * sizeof(float);
-    Guard g(m->first);
-    if (!m->frame) hcheck(hipMalloc((void**)&m->frame, bytes), "hipMalloc(frame)");
+    DeviceGuard g(m->first);
+    if (!m->frame) check(hipMalloc((void**)&m->frame, bytes), "hipMalloc(frame)");
     enqueue(m, p, precision, rng, trace, m->frame, m->host_stream);
-    hcheck(hipMemcpyAsync(host_out, m->frame, bytes, hipMemcpyDeviceToHost, m->host_stream), "hipMemcpyAsync(frame)");
-    hcheck(hipStreamSynchronize(m->host_stream), "multi-GPU render");
+    check(hipMemcpyAsync(host_out, m->frame, bytes, hipMemcpyDeviceToHost, m->host_stream), "hipMemcpyAsync(frame)");
+    check(hipStreamSynchronize(m->host_stream), "multi-GPU render");
 }
 
 size_t gpu_multi_timings(MultiRender* m, float* out, size_t n) {
@@ -469,16 +455,16 @@ size_t gpu_multi_timings(MultiRender* m, float* out, size_t n) {
     for (int d = 0; d <= m->n + 1; ++d) {
         float ms = 0.0f;
         if (d < m->n) {
-            Guard g(m->dev_of(d));
-            hcheck(hipEventSynchronize(m->dev[(size_t)d].t1[s]), "hipEventSynchronize");
-            hcheck(hipEventElapsedTime(&ms, m->dev[(size_t)d].t0[s], m->dev[(size_t)d].t1[s]), "hipEventElapsedTime");
+            DeviceGuard g(m->dev_of(d));
+            check(hipEventSynchronize(m->dev[(size_t)d].t1[s]), "hipEventSynchronize");
+            check(hipEventElapsedTime(&ms, m->dev[(size_t)d].t0[s], m->dev[(size_t)d].t1[s]), "hipEventElapsedTime");
         } else if (d == m->n) {
-            Guard g(m->first);
-            hcheck(hipEventSynchronize(m->g1[s]), "hipEventSynchronize");
-            hcheck(hipEventElapsedTime(&ms, m->g0[s], m->g1[s]), "hipEventElapsedTime");
+            DeviceGuard g(m->first);
+            check(hipEventSynchronize(m->g1[s]), "hipEventSynchronize");
+            check(hipEventElapsedTime(&ms, m->g0[s], m->g1[s]), "hipEventElapsedTime");
         } else if (m->w_armed && m->w_frames > 1) {  // window start -> last completion, per frame
-            Guard g(m->first);
-            hcheck(hipEventElapsedTime(&ms, m->w0, m->g1[s]), "hipEventElapsedTime");
+            DeviceGuard g(m->first);
+            check(hipEventElapsedTime(&ms, m->w0, m->g1[s]), "hipEventElapsedTime");
             ms /= (float)m->w_frames;
         }
         if ((size_t)d < n) out[d] = ms;

@@ -17,6 +17,7 @@
 
 #include "flatten.hpp"
 #include "gpu.hpp"
+#include "hip_util.hpp"
 #include "nrt.h"
 
 // =====================================================================
@@ -25,10 +26,6 @@
 namespace nrt {
 
 namespace {
-
-void check(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string("HIP error in ") + what + ": " + hipGetErrorString(e));
-}
 
 template <typename T>
 T* upload(const std::vector<T>& v, const char* what) {
@@ -66,23 +63,6 @@ struct DeviceScene {
     mutable std::atomic<uint32_t> queue_next{0};
 };
 constexpr uint32_t QUEUE_SLOTS = 256;
-
-// Makes `device` current for a scope and restores the caller's device afterwards: the
-// library never leaves the caller's (e.g. torch's) current device changed, and every
-// allocation, memset and launch goes to the device the scene lives on.
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int device) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (device != prev) check(hipSetDevice(device), "hipSetDevice");
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
 
 int gpu_device_count() {
     int n = 0;
@@ -220,11 +200,11 @@ DeviceScene* gpu_upload_scene(const FlatScene& fs, int device) {
 
 void gpu_free_scene(DeviceScene* ds) {
     if (!ds) return;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(ds->device);
-    for (void* p : ds->allocations) (void)hipFree(p);
-    (void)hipSetDevice(prev);
+    try {
+        DeviceGuard guard(ds->device);
+        for (void* p : ds->allocations) (void)hipFree(p);
+    } catch (...) {  // (the device cannot be made current: nothing of it is left to free)
+    }
     delete ds;
 }
 

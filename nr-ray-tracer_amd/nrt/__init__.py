@@ -681,25 +681,35 @@ def to_rgb8(img: np.ndarray, gamma: float = 0.5) -> np.ndarray:
     return out
 
 
+def _frame_args(name, first, colour, albedo, normal, depth, out, variance_out, shape=None):
+    """The validated contiguous float32 arrays (colour, albedo, normal, depth, out, variance_out) of a denoiser call
+    and their pointers; `name` prefixes the messages, `first` is the colour argument's name, `shape` the (rows, W, 3)
+    the frame must have (None: any)."""
+    c, a, n, z = (x if x.dtype == np.float32 and x.flags.c_contiguous else np.ascontiguousarray(x, dtype=np.float32)
+                  for x in (colour, albedo, normal, depth))
+    ok = c.shape == shape if shape else c.ndim == 3 and c.shape[2] == 3
+    if not ok or a.shape != c.shape or n.shape != c.shape or z.shape != c.shape[:2]:
+        raise NrtError(-1, f"{name}: {first} {c.shape}, albedo {a.shape}, normal {n.shape}, depth {z.shape} do not "
+                           f"describe one {shape or '(rows, W, 3)'} frame")
+    if out is None:
+        out = np.empty_like(c)
+    elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != c.shape:
+        raise NrtError(-1, f"{name}: out must be a contiguous float32 array of the frame's shape")
+    v = variance_out
+    if v is not None and (v.dtype != np.float32 or not v.flags.c_contiguous or v.shape != c.shape[:2]):
+        raise NrtError(-1, f"{name}: variance_out must be a contiguous float32 array of shape (rows, W)")
+    arrays = (c, a, n, z, out, v)
+    return arrays, [x.ctypes.data_as(C.POINTER(C.c_float)) if x is not None else None for x in arrays]
+
+
 def denoise(colour: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth: np.ndarray, iterations: int = 5,
             sigma_color: float = 0.6, sigma_normal: float = 0.3, sigma_depth: float = 0.5, device: int = -1,
             out: Optional[np.ndarray] = None) -> np.ndarray:
     """Edge-avoiding a-trous filter (nrt_denoise) of a (rows, W, 3) frame with its feature buffers (albedo and
     normal (rows, W, 3), depth (rows, W)); `out` may be `colour` (in place).  Needs no scene."""
-    def f32(a):
-        return a if a.dtype == np.float32 and a.flags.c_contiguous else np.ascontiguousarray(a, dtype=np.float32)
-
-    c, a, n, z = f32(colour), f32(albedo), f32(normal), f32(depth)
-    if c.ndim != 3 or c.shape[2] != 3 or a.shape != c.shape or n.shape != c.shape or z.shape != c.shape[:2]:
-        raise NrtError(-1, f"denoise: colour {c.shape}, albedo {a.shape}, normal {n.shape}, depth {z.shape} do not "
-                           "describe one (rows, W, 3) frame")
-    if out is None:
-        out = np.empty_like(c)
-    elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != c.shape:
-        raise NrtError(-1, "denoise: out must be a contiguous float32 array of the frame's shape")
+    (c, _, _, _, out, _), p = _frame_args("denoise", "colour", colour, albedo, normal, depth, out, None)
     d = _DenoiseOpts(iterations, sigma_color, sigma_normal, sigma_depth)
-    ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
-    _check(lib().nrt_denoise(ptr(c), ptr(a), ptr(n), ptr(z), c.shape[1], c.shape[0], C.byref(d), device, ptr(out)))
+    _check(lib().nrt_denoise(*p[:4], c.shape[1], c.shape[0], C.byref(d), device, p[4]))
     return out
 
 
@@ -709,24 +719,9 @@ def denoise_vg(colour: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth
     """Variance-guided a-trous filter (nrt_denoise_vg; SVGF's spatial filter with its 7x7 variance estimate) of a
     (rows, W, 3) frame with its feature buffers, as `denoise`; `variance_out`, a (rows, W) float32 array, receives
     the filtered variance of the demodulated luminance."""
-    def f32(a):
-        return a if a.dtype == np.float32 and a.flags.c_contiguous else np.ascontiguousarray(a, dtype=np.float32)
-
-    c, a, n, z = f32(colour), f32(albedo), f32(normal), f32(depth)
-    if c.ndim != 3 or c.shape[2] != 3 or a.shape != c.shape or n.shape != c.shape or z.shape != c.shape[:2]:
-        raise NrtError(-1, f"denoise_vg: colour {c.shape}, albedo {a.shape}, normal {n.shape}, depth {z.shape} do "
-                           "not describe one (rows, W, 3) frame")
-    if out is None:
-        out = np.empty_like(c)
-    elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != c.shape:
-        raise NrtError(-1, "denoise_vg: out must be a contiguous float32 array of the frame's shape")
-    v = variance_out
-    if v is not None and (v.dtype != np.float32 or not v.flags.c_contiguous or v.shape != c.shape[:2]):
-        raise NrtError(-1, "denoise_vg: variance_out must be a contiguous float32 array of shape (rows, W)")
+    (c, _, _, _, out, _), p = _frame_args("denoise_vg", "colour", colour, albedo, normal, depth, out, variance_out)
     d = _DenoiseVgOpts(iterations, sigma_luminance, sigma_normal, sigma_depth)
-    ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
-    _check(lib().nrt_denoise_vg(ptr(c), ptr(a), ptr(n), ptr(z), c.shape[1], c.shape[0], C.byref(d), device, ptr(out),
-                                ptr(v) if v is not None else None))
+    _check(lib().nrt_denoise_vg(*p[:4], c.shape[1], c.shape[0], C.byref(d), device, p[4], p[5]))
     return out
 
 
@@ -768,25 +763,10 @@ class History:
         """The next frame of the sequence (nrt_denoise_temporal): buffers as `denoise_vg`, `camera` the one the
         frame and its feature buffers were rendered with; iterations 2..5; sigmas: sigma_luminance,
         sigma_normal, sigma_depth, alpha_min, tau_z, tau_n."""
-        def f32(a):
-            return a if a.dtype == np.float32 and a.flags.c_contiguous else np.ascontiguousarray(a, dtype=np.float32)
-
-        c, a, n, z = f32(frame), f32(albedo), f32(normal), f32(depth)
-        shape = (self.rows, self.width, 3)
-        if c.shape != shape or a.shape != shape or n.shape != shape or z.shape != shape[:2]:
-            raise NrtError(-1, f"History.denoise: frame {c.shape}, albedo {a.shape}, normal {n.shape}, depth {z.shape} "
-                               f"do not describe one {shape} frame")
-        if out is None:
-            out = np.empty_like(c)
-        elif out.dtype != np.float32 or not out.flags.c_contiguous or out.shape != shape:
-            raise NrtError(-1, "History.denoise: out must be a contiguous float32 array of the frame's shape")
-        v = variance_out
-        if v is not None and (v.dtype != np.float32 or not v.flags.c_contiguous or v.shape != shape[:2]):
-            raise NrtError(-1, "History.denoise: variance_out must be a contiguous float32 array of shape (rows, W)")
-        ptr = lambda x: x.ctypes.data_as(C.POINTER(C.c_float))  # noqa: E731
-        _check(lib().nrt_denoise_temporal(self._h, C.byref(camera._c()), ptr(c), ptr(a), ptr(n), ptr(z),
-                                          C.byref(self._opts(iterations, **sigmas)), ptr(out),
-                                          ptr(v) if v is not None else None))
+        (_, _, _, _, out, _), p = _frame_args("History.denoise", "frame", frame, albedo, normal, depth, out, variance_out,
+                                              (self.rows, self.width, 3))
+        _check(lib().nrt_denoise_temporal(self._h, C.byref(camera._c()), *p[:4],
+                                          C.byref(self._opts(iterations, **sigmas)), p[4], p[5]))
         self.frames += 1
         return out
 

@@ -205,6 +205,31 @@ def test_plumbing_render_denoise_shards_and_device_entry_points():
         assert np.array_equal(dev[k].cpu().numpy(), aov[k])
 
 
+@pytest.mark.gpu
+def test_scene_scratch_grows_and_is_reused():
+    """The scene owns one scratch per filter and device: 9 x 6, then 33 x 17 (it grows), then 9 x 6 again (it is kept),
+    the two filters interleaved so that both slots live at once; every result is the host call's, bit for bit."""
+    torch = pytest.importorskip("torch")  # nrt.lib() already imported it first: one HIP runtime
+    b = nrt.Builder()
+    scene = b.finish(b.bvh([b.sphere((0, 0, 0), 1.0, b.lambertian(b.solid((1, 1, 1))))]))
+    st = torch.cuda.current_stream(0).cuda_stream
+    for shape in ((6, 9), (17, 33), (6, 9)):
+        frame, _ = case(shape, 5)
+        C, A, N, Z = (torch.from_numpy(x.copy()).to("cuda:0") for x in frame)  # (the cases are read-only)
+        var = np.empty(shape, np.float32)
+        want, want_vg = nrt.denoise(*frame), nrt.denoise_vg(*frame, variance_out=var)
+        out, dvar = torch.empty_like(C), torch.empty_like(Z)
+        scene.denoise_device(C.data_ptr(), A.data_ptr(), N.data_ptr(), Z.data_ptr(), shape[1], shape[0], out.data_ptr(),
+                             device=0, stream=st)
+        torch.cuda.synchronize(0)
+        assert np.array_equal(out.cpu().numpy(), want)
+        scene.denoise_vg_device(C.data_ptr(), A.data_ptr(), N.data_ptr(), Z.data_ptr(), shape[1], shape[0],
+                                out.data_ptr(), dvar.data_ptr(), device=0, stream=st)
+        torch.cuda.synchronize(0)
+        assert np.array_equal(out.cpu().numpy(), want_vg)
+        assert np.array_equal(dvar.cpu().numpy(), var)
+
+
 def test_argument_errors_and_missing_device():
     c = np.ones((4, 5, 3), np.float32)
     if nrt.device_count() == 0:
@@ -217,7 +242,10 @@ def test_argument_errors_and_missing_device():
     for bad in (lambda: nrt.denoise(c, c, c, c[..., 0], iterations=6),
                 lambda: nrt.denoise(c, c, c[:3], c[..., 0]),
                 lambda: nrt.denoise(c, c, c, c[:, :4, 0]),
+                lambda: nrt.denoise(c, c, c, c[..., 0], out=np.empty(c.shape, np.float64)),
+                lambda: nrt.denoise(c, c, c, c[..., 0], out=np.empty((4, 4, 3), np.float32)),
                 lambda: scene.render_aov(cam, gpus=1)):
         with pytest.raises(nrt.NrtError) as ei:
             bad()
         assert ei.value.code == -1
+        assert "denoise:" in str(ei.value) or "gpus must be 0" in str(ei.value)  # (the feature pass's own message)

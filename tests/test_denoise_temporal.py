@@ -426,6 +426,37 @@ def test_plumbing_render_history_and_device_entry_point():
             assert np.array_equal(dvar.cpu().numpy(), var)
 
 
+@pytest.mark.gpu
+def test_denoisers_on_second_device_keep_current_device():
+    """The three host entry points run on the device asked for and leave the caller's current device unchanged (device
+    guard, hip_util.hpp), as test_render_on_second_device_keeps_current_device has it for the renderer; also after a
+    call that fails behind the device switch (a singular camera is rejected before it: the history's staging is
+    allocated on its device first)."""
+    n = nrt.device_count()
+    if n < 2:
+        pytest.skip(f"{n} GPU visible: needs two devices")
+    torch = pytest.importorskip("torch")
+    shape = (6, 9)
+    cams = cameras_a(*shape)[:2]
+    frames = [planes_frame(c, PLANES_A, 600 + i) for i, c in enumerate(cams)]
+    torch.cuda.set_device(0)
+    want = nrt.denoise(*frames[0], device=0)
+    assert np.array_equal(nrt.denoise(*frames[0], device=1), want)
+    assert torch.cuda.current_device() == 0
+    want = nrt.denoise_vg(*frames[0], device=0)
+    assert np.array_equal(nrt.denoise_vg(*frames[0], device=1), want)
+    assert torch.cuda.current_device() == 0
+    h0, h1 = nrt.History(shape[1], shape[0], device=0), nrt.History(shape[1], shape[0], device=1)
+    for cam, frame in zip(cams, frames):
+        want = h0.denoise(*frame, cam)
+        assert np.array_equal(h1.denoise(*frame, cam), want)
+        assert torch.cuda.current_device() == 0
+    flat = dataclasses.replace(cams[0], pixel_delta_v=cams[0].pixel_delta_u)  # du = dv: a singular camera
+    with pytest.raises(nrt.NrtError):
+        nrt.History(shape[1], shape[0], device=1).denoise(*frames[0], flat)
+    assert torch.cuda.current_device() == 0
+
+
 def test_argument_errors_and_missing_device():
     c = np.ones((4, 5, 3), np.float32)
     cam = nrt.CameraBuilder(width=5, height=4, samples_per_pixel=1).build()
@@ -437,7 +468,14 @@ def test_argument_errors_and_missing_device():
     for bad in (lambda: hist.denoise(c, c, c, c[..., 0], cam, iterations=1),
                 lambda: hist.denoise(c, c, c, c[..., 0], cam, iterations=6),
                 lambda: hist.denoise(c, c, c, c[..., 0], nrt.CameraBuilder(width=4, height=4, samples_per_pixel=1).build()),
-                lambda: hist.denoise(c, c, c, c[..., 0], cam, variance_out=np.empty((4, 4), np.float32))):
+                lambda: hist.denoise(c, c, c, c[..., 0], cam, variance_out=np.empty((4, 4), np.float32)),
+                lambda: hist.denoise(c, c, c, c[..., 0], cam, variance_out=np.empty((4, 5), np.float64)),
+                lambda: hist.denoise(c, c, c, c[..., 0], cam, out=np.empty(c.shape, np.float64)),
+                lambda: hist.denoise(c, c, c, c[..., 0], cam, out=np.empty((4, 4, 3), np.float32)),
+                lambda: hist.denoise(c[:3], c[:3], c[:3], c[:3, :, 0], cam)):
         with pytest.raises(nrt.NrtError) as ei:
             bad()
         assert ei.value.code == -1
+        # (the library's own checks carry the C entry point's prefix, or nrt_denoise's for the shared upper bound)
+        msg = str(ei.value)
+        assert ("History.denoise:" in msg or "denoise_temporal:" in msg or "denoise: iterations" in msg), msg

@@ -193,10 +193,15 @@ def test_argument_errors_and_missing_device():
     for bad in (lambda: nrt.denoise_vg(c, c, c, c[..., 0], iterations=6),
                 lambda: nrt.denoise_vg(c, c, c[:3], c[..., 0]),
                 lambda: nrt.denoise_vg(c, c, c, c[:, :4, 0]),
-                lambda: nrt.denoise_vg(c, c, c, c[..., 0], variance_out=np.empty((4, 4), np.float32))):
+                lambda: nrt.denoise_vg(c, c, c, c[..., 0], variance_out=np.empty((4, 4), np.float32)),
+                lambda: nrt.denoise_vg(c, c, c, c[..., 0], variance_out=np.empty((4, 5), np.float64)),
+                lambda: nrt.denoise_vg(c, c, c, c[..., 0], out=np.empty(c.shape, np.float64)),
+                lambda: nrt.denoise_vg(c, c, c, c[..., 0], out=np.empty((4, 4, 3), np.float32))):
         with pytest.raises(nrt.NrtError) as ei:
             bad()
         assert ei.value.code == -1
+        # (the iteration bound is the library's check, shared with nrt_denoise, and carries its prefix)
+        assert ("denoise:" if "iterations" in str(ei.value) else "denoise_vg:") in str(ei.value)
     b = nrt.Builder()
     scene = b.finish(b.bvh([b.sphere((0, 0, 0), 1.0, b.lambertian(b.solid((1, 1, 1))))]))
     with pytest.raises(ValueError):
