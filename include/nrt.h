@@ -165,8 +165,11 @@ const char* nrt_build_id(void);
  * error of the render call instead of a fallback to the generic kernel).  The first such render
  * of a scene pays the compile (0.2-0.5 s) inside the render call, unless the on-disk code-object
  * cache holds it (NRT_JIT_CACHE = a directory, default $XDG_CACHE_HOME/nrt-jit or
- * ~/.cache/nrt-jit; "0" turns it off): keyed by the library's build id, the architecture, the
- * template arguments and the compile options, written atomically and verified on load.
+ * ~/.cache/nrt-jit; "0" turns it off): keyed by the library's build id, a hash of the embedded
+ * device headers, the hiprtc and HIP runtime versions, the architecture, the template arguments
+ * (the scene's geometry signature and its shading signature: the material kinds its materials
+ * use and the camera's mode, defocus on or off and spp > 1, so a render with another camera mode
+ * builds or loads another kernel) and the compile options, written atomically and verified on load.
  * out[0] = kernels built by hiprtc in this process, out[1] = renders that used a specialised
  * kernel, out[2] = builds that failed (the generic kernel rendered instead: slower, the same
  * frame bit for bit), out[3] = compile + load wall time in ns, out[4] = code objects taken from

@@ -1192,6 +1192,21 @@ struct BvhSig {
     static constexpr bool lstack = false;
     static constexpr bool persist = false;
 };
+// Shading signature of a scene-specialised kernel (jit.hip): the material kinds the scene's materials
+// use (bit 1 << MAT_*) and the camera's mode at this launch (SHADE_DEFOCUS: a non-zero defocus disk,
+// SHADE_MULTI: spp > 1), so the arms of surface / scatter_ray / camera that the scene cannot reach are
+// not compiled in; the arithmetic that stays is the generic kernel's, statement for statement.
+// SHADE_CAM_RUNTIME: the camera's mode is read from RenderParams (the ChaCha8 loops, whose camera ray
+// always draws the disk).  ShadeAny (the generic kernels): every kind, camera mode at run time.
+// (SHADE_* values: render_params.hpp)
+template <uint32_t MATS, uint32_t CAM>
+struct ShadeSig {
+    static constexpr bool has(uint32_t kind) { return ((MATS >> kind) & 1u) != 0u; }
+    static constexpr bool cam_fixed = (CAM & SHADE_CAM_RUNTIME) == 0u;
+    static constexpr bool defocus = (CAM & SHADE_DEFOCUS) != 0u, multi = (CAM & SHADE_MULTI) != 0u;
+};
+using ShadeAny = ShadeSig<0xFFFFFFFFu, SHADE_CAM_RUNTIME>;
+
 template <bool FLAT, uint32_t... RUNS>
 __device__ __forceinline__ void sig_runs(WorldSig<RUNS...>, ConstPrimWorld<float> wp, uint32_t& k, const Ray<float>& ray,
                                          const f32x2& dox, const f32x2& doy, const f32x2& doz, const float inv[3],
@@ -3005,7 +3020,8 @@ template <> struct StackEntry<true> { using type = uint16_t; };
 // RenderParams must stay the FIRST by-value parameter (kernarg offset 0): the f64 cam3 reads the camera
 // vectors straight from the kernarg segment at offsetof(RenderParams, ...) (the exact earth / C5 parity
 // cases, whose cameras are off the origin, catch a reordering).
-template <typename R, class G, int MAXD, bool EXACT, bool LDS_SCENE, int KFLAGS = 0, class SIG = NoSig>
+template <typename R, class G, int MAXD, bool EXACT, bool LDS_SCENE, int KFLAGS = 0, class SIG = NoSig,
+          class SHADE = ShadeAny>
 __global__ void __launch_bounds__(BLOCK, (min_waves_per_simd<R, G, MAXD, SIG>(KFLAGS)))
 render_kernel(const RenderParams p, const DSceneView<R> gsc) {
     constexpr bool PROF = (KFLAGS & KF_PROF) != 0;
@@ -3113,10 +3129,12 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
         }
         h = make_record<R, MAXD, EXACT, FLAT, LDS_SCENE, (KFLAGS & KF_PLANES) != 0>(sc, ray, hm);
         m = material(h.mat);
-        if (m.kind == MAT_DIFFUSE_LIGHT) {  // emit (diffuse_light.rs:62-75), no scatter
-            const R k = bounced ? m.param : R(1.0);
-            contrib = tp * (k * albedo(m, h));
-            return false;
+        if constexpr (SHADE::has(MAT_DIFFUSE_LIGHT)) {
+            if (m.kind == MAT_DIFFUSE_LIGHT) {  // emit (diffuse_light.rs:62-75), no scatter
+                const R k = bounced ? m.param : R(1.0);
+                contrib = tp * (k * albedo(m, h));
+                return false;
+            }
         }
         return true;
     };
@@ -3130,7 +3148,15 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
         V<R> dir;
         V<R> att = mk(R(1), R(1), R(1));
         bool scattered = true;
-        if (m.kind == MAT_DIELECTRIC) {
+        // the kinds the signature rules out are decided here, not by m.kind: their arms below are dead
+        // code the compiler drops (a scene-specialised kernel of a scene without them carries neither
+        // the arm, nor the kind compare, nor the exec-mask region around it)
+        constexpr bool DIELECTRIC = SHADE::has(MAT_DIELECTRIC), LAMBERTIAN = SHADE::has(MAT_LAMBERTIAN),
+                       METAL = SHADE::has(MAT_METAL);
+        bool dielectric = DIELECTRIC, lambertian = LAMBERTIAN;
+        if constexpr (DIELECTRIC && (LAMBERTIAN || METAL)) dielectric = m.kind == MAT_DIELECTRIC;
+        if constexpr (LAMBERTIAN && METAL) lambertian = m.kind == MAT_LAMBERTIAN;
+        if (dielectric) {
             const R ri = h.front ? fast_div(R(1.0), m.param) : m.param;
             const V<R> unit = normalize(ray.d);
             const R cos_theta = fmin(dot(-unit, h.n), R(1.0));
@@ -3147,7 +3173,7 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             V<R> rs;
             if constexpr (G::exact_stream) rs = have_rs ? rs_pre : random_in_unit_sphere<R>(g);
             else rs = unit_ball_inverse<R>(w.x, w.y, w.z);
-            if (m.kind == MAT_LAMBERTIAN) {
+            if (lambertian) {
                 dir = h.n + rs;
                 if (fabs(dir.x) < R(1e-8) && fabs(dir.y) < R(1e-8) && fabs(dir.z) < R(1e-8)) dir = h.n;
             } else {  // metal: draws even when fuzz = 0 (Q5)
@@ -3658,7 +3684,13 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
         auto camera = [&]() {
             const uint32_t px = pxy & 0xFFFFu, py = pxy >> 16;
             R ox = R(0), oy = R(0);
-            if (p.spp > 1) {
+            // the camera's mode: constants of a scene-specialised kernel (ShadeSig), else the launch's
+            bool jitter = SHADE::multi, defocus = SHADE::defocus;
+            if constexpr (!SHADE::cam_fixed) {
+                jitter = p.spp > 1;
+                defocus = p.defocus != 0;
+            }
+            if (jitter) {
                 if constexpr (sizeof(R) == 4) {
                     ox = u12(w.x) - 1.5f;
                     oy = u12(w.y) - 1.5f;
@@ -3668,7 +3700,7 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
                 }
             }
             const V<R> point = vfma((R)py + oy, cam(2), vfma((R)px + ox, cam(1), cam(0)));
-            if (p.defocus) {
+            if (defocus) {
                 const uint4 wd = G::template block_at<R>(pixel_index(), cur, G::template defocus_step<R>());
                 const V<R> disk = unit_disk_inverse<R>(wd.x, wd.y);
                 ray.o = vfma(disk.y, cam(5), vfma(disk.x, cam(4), cam(3)));
@@ -3803,7 +3835,11 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             // claimed sample's camera block (pixel', sample', 0)
             w = G::template block_at<R>(pixel_index(), cur, scatter ? b + 1u : 0u);
             const unsigned long long t3 = stamp();
-            if (scatter && !scatter_ray(h)) killed = true;
+            if constexpr (SHADE::has(MAT_METAL)) {
+                if (scatter && !scatter_ray(h)) killed = true;
+            } else {  // only a metal absorbs
+                if (scatter) scatter_ray(h);
+            }
             if (want && alive) {
                 camera();
                 killed = pxy == PAD_XY;  // padding sample: no pixel, ends at once

@@ -1,5 +1,7 @@
-// Fast kernels (Real = float).  Built with -ffp-contract=fast; divisions on
-// the hot path use the hardware reciprocal (kernel.hpp fast_div / fast_rcp).
+// Fast kernels (Real = float).  Built with -ffp-contract=on (Makefile FAST_CONTRACT, shared with the
+// hiprtc-built scene-specialised kernels so both fuse the same FMAs); divisions on the hot path use
+// the hardware reciprocal (kernel.hpp fast_div / fast_rcp).  The generic kernels here keep every
+// material kind and read the camera's mode at run time (kernel.hpp ShadeAny).
 #include "kernel.hpp"
 #include "launch.hpp"
 #include "launch_impl.hpp"

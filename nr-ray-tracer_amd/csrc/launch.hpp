@@ -1,6 +1,6 @@
 // Kernel launchers, one translation unit per numeric contract:
 //   kernels_exact.hip  (f64, -ffp-contract=off: the reference's un-fused arithmetic)
-//   kernels_fast.hip   (f32, -ffp-contract=fast + hardware reciprocals)
+//   kernels_fast.hip   (f32, -ffp-contract=on + hardware reciprocals)
 #pragma once
 
 #include <hip/hip_runtime.h>

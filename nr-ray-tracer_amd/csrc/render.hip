@@ -55,6 +55,7 @@ struct DeviceScene {
     const DPrimWorld<float>* wbvh_prims = nullptr;
     uint32_t n_wbvh_prims = 0;
     int wbvh_kinds = 0;  // WPRIMS_* of the world BVH's leaves (the scene-specialised kernel's BvhSig)
+    uint32_t mat_kinds = 0;  // bit 1 << MAT_* per material kind in the scene (the scene-specialised kernel's ShadeSig)
     std::vector<uint32_t> wruns;  // the world list's run words (scene-specialised kernel, jit.hip)
     // Philox group-queue heads: each launch takes the next of QUEUE_SLOTS sets of
     // QUEUE_HEADS per-XCD heads and zeroes it on its own stream (up to QUEUE_SLOTS
@@ -167,6 +168,7 @@ DeviceScene* gpu_upload_scene(const FlatScene& fs, int device) {
         for (const DTexture& t : fs.textures)
             ds->texpal &= t.kind == TEX_SOLID || (t.kind == TEX_IMAGE && t.format == TEXFMT_PAL16);
         for (const DMatFast& m : fs.mats_fast) ds->flat &= m.solid != 0;
+        for (const DMatFast& m : fs.mats_fast) ds->mat_kinds |= 1u << m.kind;
         // unit kinds from the runs (box / room units also hold header and empty face slots)
         for (uint32_t run : fs.wruns)
             ds->flat &= (run & WRUN_KIND_MASK) != PRIM_SPHERE && (run & WRUN_KIND_MASK) != PRIM_SPHERE32;
@@ -306,13 +308,20 @@ void gpu_launch_render(const DeviceScene* ds, const RenderParams& p, uint32_t pr
                                 std::to_string(maxd) + ", false, " +
                                 (staged ? "true, " : "false, ") +
                                 std::to_string(ds->flat ? dev::KF_FLAT : (ds->texpal ? dev::KF_TEXPAL : 0)) + ", ";
+            // shading signature (kernel.hpp ShadeSig), from this scene's materials and this launch's
+            // camera: a render with another camera mode (defocus, spp 1) asks for another variant here,
+            // so a kernel never runs with facts its launch does not have.  The ChaCha8 loops read the
+            // camera's mode at run time (one variant per scene)
+            const uint32_t cam_sig = rng == RNG_PHILOX ? (q.defocus ? dev::SHADE_DEFOCUS : 0u) | (q.spp > 1u ? dev::SHADE_MULTI : 0u)
+                                                       : dev::SHADE_CAM_RUNTIME;
+            const std::string shade = ", nrt::dev::ShadeSig<" + std::to_string(ds->mat_kinds) + "u, " + std::to_string(cam_sig) + "u>";
             if (maxd == MODE_WORLD_LIST) {
                 // ChaCha8 keeps the generic world-list kernel: its specialised build measured
                 // 1.85x slower on C5 (72 -> 133 ms), the Philox one 1.25x faster
                 if (rng == RNG_PHILOX && !ds->wruns.empty() && ds->wruns.size() <= JIT_MAX_RUNS) {
                     targs += "nrt::dev::WorldSig<";
                     for (size_t i = 0; i < ds->wruns.size(); ++i) targs += (i ? ", " : "") + std::to_string(ds->wruns[i]) + "u";
-                    targs += ">";
+                    targs += ">" + shade;
                     jit = jit_render_kernel(targs, ds->device);
                     if (!jit) jit_require_failed(targs);
                 }
@@ -322,7 +331,7 @@ void gpu_launch_render(const DeviceScene* ds, const RenderParams& p, uint32_t pr
                 const bool compact = v.wbvh4c && !(ce && ce[0] == '0');
                 if (compact) stack_entry = 2;
                 targs += std::string("nrt::dev::BvhSig<") + (compact ? "5, " : v.wbvh4 ? "4, " : "2, ") +
-                         ((v.wflags & WFLAG_COPLANAR) ? "true, " : "false, ") + std::to_string(ds->wbvh_kinds) + ">";
+                         ((v.wflags & WFLAG_COPLANAR) ? "true, " : "false, ") + std::to_string(ds->wbvh_kinds) + ">" + shade;
                 jit = jit_render_kernel(targs, ds->device);
                 if (!jit) jit_require_failed(targs);
             }
