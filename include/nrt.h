@@ -126,7 +126,17 @@ typedef struct {
      * same bits as gpus = 0 (pixels and their RNG streams do not depend on the device).  The
      * scene owns the communicators and shard buffers (created on first use, freed with it). */
     uint32_t gpus;
-    uint32_t reserved;
+    /* Philox only: the launch renders samples sample_offset .. sample_offset + spp - 1 of every pixel (spp =
+     * the camera's samples_per_pixel) and divides their sum by spp.  A pixel's sample s draws the blocks
+     * (pixel, s, step) whatever launch renders it, so windows over disjoint ranges are independent, and the
+     * frames R(s0, m) of the windows [s0, s0 + m) compose: (a + n) R(0, a + n) = a R(0, a) + n R(a, n) up to
+     * each frame's own rounding.  0: the frame of every earlier version, bit for bit.  The pixel jitter is on
+     * when this launch's spp > 1, whatever the offset: a window of one sample goes through the pixel's
+     * centre.  NRT_E_INVALID (before any device is touched): f32 with sample_offset + spp > 2^24 (the
+     * Philox2x32 counter packs sample | step << 24), f64 with sample_offset + spp >= 2^32, and ChaCha8 with
+     * a non-zero offset (the reference stream is sequential: where a window starts depends on the lengths
+     * of the paths before it).  Row selection and gpus = N take it unchanged; nrt_render_aov* ignores it. */
+    uint32_t sample_offset;
 } nrt_render_opts;
 
 typedef struct {
@@ -168,8 +178,8 @@ const char* nrt_build_id(void);
  * ~/.cache/nrt-jit; "0" turns it off): keyed by the library's build id, a hash of the embedded
  * device headers, the hiprtc and HIP runtime versions, the architecture, the template arguments
  * (the scene's geometry signature and its shading signature: the material kinds its materials
- * use and the camera's mode, defocus on or off and spp > 1, so a render with another camera mode
- * builds or loads another kernel) and the compile options, written atomically and verified on load.
+ * use and the camera's mode, defocus on or off, spp > 1 and a sample window past 0, so a render with another
+ * camera mode builds or loads another kernel) and the compile options, written atomically and verified on load.
  * out[0] = kernels built by hiprtc in this process, out[1] = renders that used a specialised
  * kernel, out[2] = builds that failed (the generic kernel rendered instead: slower, the same
  * frame bit for bit), out[3] = compile + load wall time in ns, out[4] = code objects taken from
@@ -346,6 +356,30 @@ int nrt_denoise_vg_device(const nrt_scene* scene, const float* dev_colour, const
                           const float* dev_normal, const float* dev_depth, uint32_t width, uint32_t rows,
                           const nrt_denoise_vg_opts* dopts, int32_t device, float* dev_out, float* dev_out_variance,
                           void* hip_stream);
+/* The variance-guided filter with a dual-buffer variance estimate (reference counterpart: none).  colour_a and
+ * colour_b are two frames A, B of one camera over disjoint sample windows of equal length (nrt_render_opts.
+ * sample_offset), so their noise is independent and their mean is the frame over both windows.  a, lum, g(p, q), the
+ * passes and the sigmas as for nrt_denoise_vg:
+ *   D_0(p)   = ((A + B) / 2) / a                        per channel
+ *   delta(p) = lum((A - B) / a) / 2                     per-channel IEEE divisions, then lum
+ *   Var_0(p) = sum_q w(p, q) delta(q)^2 / sum_q w(p, q),  q = p + (dx, dy), |dx|, |dy| <= 3, w = exp(-g(p, q)),
+ *              taps outside the image skipped
+ * then nrt_denoise_vg's K passes from (D_0, Var_0): out = D_K a, out_variance (may be NULL) = Var_K.  For independent
+ * halves E[delta^2] is the variance of lum(D_0): delta^2 is a one-degree-of-freedom estimate of the noise alone, which
+ * the guide-weighted window pools; shading features the guides do not see (shadow edges, reflections) are in A and B
+ * alike and cancel, where nrt_denoise_vg's spatial spread counts them as noise.  No luminance term enters w: an edge
+ * in the image is not evidence of noise.  A == B gives a variance of exactly 0 everywhere.  Buffers as
+ * nrt_denoise_vg's; out may be colour_a or colour_b (in place), no other overlap (NRT_E_INVALID).  dopts NULL,
+ * determinism, device and synchrony as nrt_denoise. */
+int nrt_denoise_vg_dual(const float* colour_a, const float* colour_b, const float* albedo, const float* normal,
+                        const float* depth, uint32_t width, uint32_t rows, const nrt_denoise_vg_opts* dopts,
+                        int32_t device, float* out, float* out_variance);
+/* Same over device memory, K + 1 launches enqueued on `hip_stream`, asynchronous (reference counterpart: none), on the
+ * scene's variance-guided scratch (nrt_denoise_vg_device's, under its rules). */
+int nrt_denoise_vg_dual_device(const nrt_scene* scene, const float* dev_colour_a, const float* dev_colour_b,
+                               const float* dev_albedo, const float* dev_normal, const float* dev_depth, uint32_t width,
+                               uint32_t rows, const nrt_denoise_vg_opts* dopts, int32_t device, float* dev_out,
+                               float* dev_out_variance, void* hip_stream);
 /* ---- temporal accumulation in front of the variance-guided filter: SVGF (Schied et al. 2017) whole
  *      (reference counterpart: none).  The scene is static between frames, so reprojection is a
  *      function of the two cameras and the depth buffer alone. */

@@ -303,6 +303,15 @@ RenderParams make_params(const nrt_camera& c, const nrt_render_opts* o, uint32_t
         if (o->precision == NRT_PRECISION_F32 && (p.spp > PHILOX2_MAX_SPP || p.max_bounces > PHILOX2_MAX_BOUNCES))
             throw std::invalid_argument("f32 Philox mode: samples_per_pixel <= 2^24 and ray_max_bounces <= 254 "
                                         "(Philox2x32 counter (pixel, sample | step << 24))");
+        // the sample window [sample_offset, sample_offset + spp): the blocks' sample index stays in the counter
+        if (o->precision == NRT_PRECISION_F32 ? (uint64_t)o->sample_offset + p.spp > PHILOX2_MAX_SPP
+                                              : (uint64_t)o->sample_offset + p.spp > 0xFFFFFFFFull)
+            throw std::invalid_argument("sample_offset + samples_per_pixel exceeds the Philox counter's sample field "
+                                        "(f32: <= 2^24, f64: < 2^32)");
+        p.sample0 = o->sample_offset;
+    } else if (o && o->sample_offset) {
+        throw std::invalid_argument("sample_offset needs rng = Philox: a ChaCha8 stream is sequential, so a window's "
+                                    "start depends on the paths before it");
     }
     // Radiance grid 2^-k: a sample's radiance is at most max(background, emission) x
     // albedo^bounces; k keeps spp such values below 2^52, so the pixel sums are exact
@@ -786,6 +795,7 @@ RenderParams aov_params(const nrt_scene* scene, const nrt_camera* camera, const 
     if (!opts) o.device = -1;
     o.precision = NRT_PRECISION_F32;  // (the camera's f32 copy; no sample pool is sized)
     o.rng = NRT_RNG_CHACHA8;
+    o.sample_offset = 0;  // (one un-jittered ray per pixel: no window)
     RenderParams p = make_params(*camera, &o, rows, scene->flat);
     if (n_pixels < (size_t)rows * p.width) throw std::invalid_argument("feature buffers too small");
     return p;
@@ -1014,6 +1024,67 @@ int nrt_denoise_temporal(nrt_history* history, const nrt_camera* camera, const f
         st.upload(colour, albedo, normal, depth);
         temporal_run(history, t, dev, st.colour(), st.albedo(), st.normal(), st.depth(), st.colour(),
                      out_variance ? st.rest() : nullptr, nullptr);
+        st.download(out, st.colour(), 3);
+        st.download(out_variance, st.rest(), 1);
+        return NRT_OK;
+    });
+}
+
+// ---- dual-buffer variance in front of the variance-guided passes (denoise.hip, vg_dual_kernel)
+namespace {
+
+// Every check that needs no device, for the two entry points: out may be either colour buffer, no other overlap.
+DenoiseArgs dual_args(const float* ca, const float* cb, const float* a, const float* n, const float* z, uint32_t width,
+                      uint32_t rows, const nrt_denoise_vg_opts* dopts, const float* out, const float* var) {
+    if (!cb) throw std::invalid_argument("null argument");
+    const nrt_denoise_vg_opts o = dopts ? *dopts : nrt_denoise_vg_opts{};
+    const DenoiseArgs d = denoise_args(ca, a, n, z, out, width, rows, o.iterations, o.sigma_luminance, o.sigma_normal,
+                                       o.sigma_depth, 4.0f);
+    const size_t px = (size_t)width * rows;
+    const float* in[5] = {ca, cb, a, n, z};
+    const size_t len[5] = {3 * px, 3 * px, 3 * px, 3 * px, px};
+    for (int i = 0; i < 5; ++i) {
+        if ((overlap(out, 3 * px, in[i], len[i]) && !(i < 2 && out == in[i])) || overlap(var, px, in[i], len[i]))
+            throw std::invalid_argument("denoise_vg_dual: out may be colour_a or colour_b; no other overlap");
+    }
+    if (overlap(var, px, out, 3 * px)) throw std::invalid_argument("denoise_vg_dual: out_variance overlaps out");
+    return d;
+}
+
+}  // namespace
+
+int nrt_denoise_vg_dual_device(const nrt_scene* scene, const float* dev_colour_a, const float* dev_colour_b,
+                               const float* dev_albedo, const float* dev_normal, const float* dev_depth, uint32_t width,
+                               uint32_t rows, const nrt_denoise_vg_opts* dopts, int32_t device, float* dev_out,
+                               float* dev_out_variance, void* hip_stream) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        if (!scene) throw std::invalid_argument("null argument");
+        const DenoiseArgs a = dual_args(dev_colour_a, dev_colour_b, dev_albedo, dev_normal, dev_depth, width, rows, dopts,
+                                        dev_out, dev_out_variance);
+        const int dev = device_or_current(device);
+        DenoiseScratch* scratch = scene_scratch(scene, &nrt_scene::denoise_vg, dev, (size_t)width * rows, 16);
+        gpu_denoise_vg_dual(scratch, dev_colour_a, dev_colour_b, dev_albedo, dev_normal, dev_depth, width, rows,
+                            a.iterations, a.sigma_color, a.sigma_normal, a.sigma_depth, dev_out, dev_out_variance,
+                            hip_stream);
+        return NRT_OK;
+    });
+}
+
+int nrt_denoise_vg_dual(const float* colour_a, const float* colour_b, const float* albedo, const float* normal,
+                        const float* depth, uint32_t width, uint32_t rows, const nrt_denoise_vg_opts* dopts,
+                        int32_t device, float* out, float* out_variance) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        const DenoiseArgs a = dual_args(colour_a, colour_b, albedo, normal, depth, width, rows, dopts, out, out_variance);
+        const int dev = device_or_current(device);
+        const size_t n = (size_t)width * rows;
+        const FrameStaging st(n, dev, 14);  // colour A, filtered in place | ... | variance | colour B
+        float* const db = st.rest() + n;
+        const ScratchPtr scratch(gpu_denoise_scratch(nullptr, n, dev, 16), gpu_denoise_scratch_free);
+        st.upload(colour_a, albedo, normal, depth);
+        device_copy_from_host(db, colour_b, n * 3 * sizeof(float), dev);
+        gpu_denoise_vg_dual(scratch.get(), st.colour(), db, st.albedo(), st.normal(), st.depth(), width, rows,
+                            a.iterations, a.sigma_color, a.sigma_normal, a.sigma_depth, st.colour(),
+                            out_variance ? st.rest() : nullptr, nullptr);
         st.download(out, st.colour(), 3);
         st.download(out_variance, st.rest(), 1);
         return NRT_OK;

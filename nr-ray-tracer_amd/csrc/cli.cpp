@@ -220,7 +220,7 @@ void usage() {
             "       [--focal-length F] [--field-of-view DEG] [--defocus-angle DEG] [--focus-distance D]\n"
             "       [--samples-per-pixel N] [--ray-max-bounces N] [-v]\n"
             "       [--precision f64|f32] [--rng chacha8|philox] [--gpus N] [--legacy-schema]\n"
-            "       [--denoise[=K] | --denoise-vg[=K]]\n");
+            "       [--denoise[=K] | --denoise-vg[=K] | --denoise-dual[=K]] [--sample-offset N]\n");
     exit(2);
 }
 
@@ -236,6 +236,7 @@ int main(int argc, char** argv) {
     int gpus = 1;
     uint32_t denoise = 0;     // a-trous passes (0: no filter)
     uint32_t denoise_vg = 0;  // variance-guided a-trous passes (0: no filter)
+    uint32_t denoise_dual = 0;  // the same passes with the variance taken between two half-sample frames
     nrt_camera_config cc{};
     nrt_render_opts opts{};
     opts.device = -1;
@@ -286,12 +287,25 @@ int main(int argc, char** argv) {
             denoise_vg = (uint32_t)atoi(a.c_str() + 13);
             if (denoise_vg < 1 || denoise_vg > 5) die("--denoise-vg=K: K must be 1..5");
         }
+        else if (a == "--denoise-dual") denoise_dual = 5;
+        else if (a.rfind("--denoise-dual=", 0) == 0) {
+            denoise_dual = (uint32_t)atoi(a.c_str() + 15);
+            if (denoise_dual < 1 || denoise_dual > 5) die("--denoise-dual=K: K must be 1..5");
+        }
+        else if (a == "--sample-offset") {
+            const std::string v = val();
+            char* end = nullptr;
+            const unsigned long long x = strtoull(v.c_str(), &end, 10);
+            if (v.empty() || *end || x > 0xFFFFFFFFull) die("invalid value '" + v + "' for --sample-offset");
+            opts.sample_offset = (uint32_t)x;
+        }
         else if (a.rfind("--", 0) == 0) kv.emplace_back(a, val());
         else if (scene.empty()) scene = a;
         else usage();
     }
     if (scene.empty()) usage();
-    if (denoise && denoise_vg) die("--denoise and --denoise-vg are mutually exclusive");
+    if ((denoise != 0) + (denoise_vg != 0) + (denoise_dual != 0) > 1)
+        die("--denoise, --denoise-vg and --denoise-dual are mutually exclusive");
     for (auto& kvp : kv) {
         const std::string& k = kvp.first;
         const std::string& v = kvp.second;
@@ -331,6 +345,16 @@ int main(int argc, char** argv) {
     if (nrt_scene_load_ex(scene.c_str(), &cc, load_flags, &sc, &cam) != NRT_OK) die(nrt_last_error());
     const uint32_t W = (uint32_t)cam.width, H = (uint32_t)cam.height;
     std::vector<float> img((size_t)W * H * 3);
+    // --denoise-dual: the frame as two renders of half the samples each, windows [s0, s0 + spp/2) and
+    // [s0 + spp/2, s0 + spp) (nrt_render_opts.sample_offset); the second goes into img_b
+    std::vector<float> img_b;
+    const uint64_t spp_all = cam.samples_per_pixel;
+    if (denoise_dual) {
+        if (spp_all % 2 || spp_all < 4)
+            die("--denoise-dual halves the samples: samples_per_pixel must be even and >= 4 (each half jitters)");
+        cam.samples_per_pixel = spp_all / 2;
+        img_b.resize(img.size());
+    }
 
     // GPU runtime start, the scene's upload and (--gpus N > 1) the multi-GPU context before the timed
     // render (render.rs:57-62 times scene.render alone; the scene was built before it), reported apart
@@ -368,31 +392,39 @@ int main(int argc, char** argv) {
     }
     const double init_secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - ti).count();
     const auto t0 = std::chrono::steady_clock::now();
-    if (shards) {
-        std::vector<std::vector<float>> part((size_t)gpus);
-        std::vector<std::string> err((size_t)gpus);
-        std::vector<std::thread> th;
-        for (int g = 0; g < gpus; ++g)
-            th.emplace_back([&, g]() {
-                nrt_render_opts o = opts;
-                o.device = dev_of(g);
-                o.row_offset = (uint32_t)g;
-                o.row_stride = (uint32_t)gpus;
-                part[(size_t)g].resize((size_t)nrt_rows_selected(H, &o) * W * 3);
-                if (nrt_render(sc, &cam, &o, part[(size_t)g].data(), part[(size_t)g].size(), nullptr, nullptr) != NRT_OK)
-                    err[(size_t)g] = nrt_last_error();
-            });
-        for (auto& t : th) t.join();
-        for (const auto& e : err)
-            if (!e.empty()) die(e);
-        for (uint32_t y = 0; y < H; ++y)  // frame row y = shard y % N, its row y / N
-            memcpy(&img[(size_t)y * W * 3], &part[y % (uint32_t)gpus][(size_t)(y / (uint32_t)gpus) * W * 3],
-                   (size_t)W * 3 * sizeof(float));
-    } else if (nrt_render(sc, &cam, &opts, img.data(), img.size(), nullptr, nullptr) != NRT_OK) {
-        die(nrt_last_error());
+    auto render_frame = [&](std::vector<float>& img) {  // the frame of (cam, opts), whichever way the devices share it
+        if (shards) {
+            std::vector<std::vector<float>> part((size_t)gpus);
+            std::vector<std::string> err((size_t)gpus);
+            std::vector<std::thread> th;
+            for (int g = 0; g < gpus; ++g)
+                th.emplace_back([&, g]() {
+                    nrt_render_opts o = opts;
+                    o.device = dev_of(g);
+                    o.row_offset = (uint32_t)g;
+                    o.row_stride = (uint32_t)gpus;
+                    part[(size_t)g].resize((size_t)nrt_rows_selected(H, &o) * W * 3);
+                    if (nrt_render(sc, &cam, &o, part[(size_t)g].data(), part[(size_t)g].size(), nullptr, nullptr) != NRT_OK)
+                        err[(size_t)g] = nrt_last_error();
+                });
+            for (auto& t : th) t.join();
+            for (const auto& e : err)
+                if (!e.empty()) die(e);
+            for (uint32_t y = 0; y < H; ++y)  // frame row y = shard y % N, its row y / N
+                memcpy(&img[(size_t)y * W * 3], &part[y % (uint32_t)gpus][(size_t)(y / (uint32_t)gpus) * W * 3],
+                       (size_t)W * 3 * sizeof(float));
+        } else if (nrt_render(sc, &cam, &opts, img.data(), img.size(), nullptr, nullptr) != NRT_OK) {
+            die(nrt_last_error());
+        }
+    };
+    render_frame(img);
+    if (denoise_dual) {
+        if ((uint64_t)opts.sample_offset + spp_all > 0xFFFFFFFFull) die("--sample-offset + samples_per_pixel exceeds 2^32 - 1");
+        opts.sample_offset += (uint32_t)cam.samples_per_pixel;
+        render_frame(img_b);
     }
     const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    if (denoise || denoise_vg) {  // before the output stage: feature buffers on the first device, the frame filtered in place
+    if (denoise || denoise_vg || denoise_dual) {  // before the output stage: feature buffers on the first device, the frame filtered in place
         const auto td = std::chrono::steady_clock::now();
         const size_t n = (size_t)W * H;
         std::vector<float> albedo(n * 3), normal(n * 3), depth(n);
@@ -402,20 +434,22 @@ int main(int argc, char** argv) {
         nrt_denoise_opts dopts{};
         dopts.iterations = denoise;
         nrt_denoise_vg_opts vopts{};
-        vopts.iterations = denoise_vg;
+        vopts.iterations = denoise_vg + denoise_dual;
         if (nrt_render_aov(sc, &cam, &ao, albedo.data(), normal.data(), depth.data(), n) != NRT_OK ||
-            (denoise_vg ? nrt_denoise_vg(img.data(), albedo.data(), normal.data(), depth.data(), W, H, &vopts, ao.device,
+            (denoise_dual ? nrt_denoise_vg_dual(img.data(), img_b.data(), albedo.data(), normal.data(), depth.data(), W, H,
+                                                &vopts, ao.device, img.data(), nullptr)
+             : denoise_vg ? nrt_denoise_vg(img.data(), albedo.data(), normal.data(), depth.data(), W, H, &vopts, ao.device,
                                          img.data(), nullptr)
                         : nrt_denoise(img.data(), albedo.data(), normal.data(), depth.data(), W, H, &dopts, ao.device,
                                       img.data())) != NRT_OK)
             die(nrt_last_error());
         if (verbose)
-            fprintf(stderr, " Denoising (%u%s passes) - Done in %.3f secs\n", denoise + denoise_vg,
-                    denoise_vg ? " variance-guided" : "",
+            fprintf(stderr, " Denoising (%u%s passes) - Done in %.3f secs\n", denoise + denoise_vg + denoise_dual,
+                    denoise_dual ? " variance-guided, dual-buffer variance" : denoise_vg ? " variance-guided" : "",
                     std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count());
     }
     if (verbose) {
-        const double samples = (double)W * H * (double)cam.samples_per_pixel;
+        const double samples = (double)W * H * (double)spp_all;
         fprintf(stderr, " GPU runtime start + scene upload: %.3f secs\n", init_secs);
         fprintf(stderr, " Rendering - Done in %.3f secs (%.1f Msamples/s)\n", secs, samples / secs / 1e6);
     }

@@ -352,8 +352,12 @@ __device__ __forceinline__ float lum(float r, float g, float b) {
 // (4 B + 16 B, 10.6 KB).  Consecutive lanes read consecutive words / records at every tap, so neither
 // array has a bank conflict.  Each lane sums its 49 taps in one fixed order; the luminance is shifted
 // by the centre's, so the two moments stay of the noise's size and their difference does not cancel.
-// (The two halves below are shared with temporal_kernel.)
-__device__ __forceinline__ void vg_stage(const VgParams& p, float4* sg, float* sl, int tx0, int ty0, int tid) {
+// (The two halves below are shared with temporal_kernel; the staging loop, with another word per slot, with
+// vg_dual_kernel.)
+// Stage the region's guide records and one word per slot, word(a) of pixel a; slots outside the image hold zeros.
+template <class F>
+__device__ __forceinline__ void vg_stage_words(const VgParams& p, float4* sg, float* sl, int tx0, int ty0, int tid,
+                                               F&& word) {
     const int W = (int)p.width, H = (int)p.height;
     for (int q = tid; q < VPIX; q += THREADS) {
         const int v = q / VW, u = q - v * VW;
@@ -363,12 +367,19 @@ __device__ __forceinline__ void vg_stage(const VgParams& p, float4* sg, float* s
         if (in_range(x, W) && in_range(y, H)) {
             const size_t a = (size_t)y * p.width + (size_t)x;
             r = load_guide(p, a);
-            l = lum(demodulate(p.colour, p.albedo, 3 * a), demodulate(p.colour, p.albedo, 3 * a + 1),
-                    demodulate(p.colour, p.albedo, 3 * a + 2));
+            l = word(a);
         }
         sg[q] = r;
         sl[q] = l;
     }
+}
+
+// the word of the moments and the temporal kernel: the demodulated luminance
+__device__ __forceinline__ void vg_stage(const VgParams& p, float4* sg, float* sl, int tx0, int ty0, int tid) {
+    vg_stage_words(p, sg, sl, tx0, ty0, tid, [&](size_t a) {
+        return lum(demodulate(p.colour, p.albedo, 3 * a), demodulate(p.colour, p.albedo, 3 * a + 1),
+                   demodulate(p.colour, p.albedo, 3 * a + 2));
+    });
 }
 
 // Var_0 of the pixel (px, py) at region slot cq
@@ -418,6 +429,70 @@ __global__ void __launch_bounds__(THREADS) vg_moments_kernel(const VgParams p) {
     p.rout[pix] = make_float4(demodulate(p.colour, p.albedo, 3 * pix), demodulate(p.colour, p.albedo, 3 * pix + 1),
                               demodulate(p.colour, p.albedo, 3 * pix + 2), var0);
     p.gout[pix] = sg[cq];
+}
+
+// ---- dual-buffer variance: Var_0 from two frames A, B of one camera over disjoint sample windows of equal
+//      length (formula: nrt.h, nrt_denoise_vg_dual).  The moments kernel's place in the chain and its contract:
+//      it writes (D_0.rgb, Var_0) and the packed guide record of every pixel, and the passes follow unchanged.
+struct VgDualParams {
+    VgParams v;           // colour = A, albedo, normal, depth, width, height, kn, kz, rout, gout
+    const float* colour_b;
+};
+
+// (A[i] + B[i]) / 2 over max(albedo, floor), and the half difference's channel before the luminance
+__device__ __forceinline__ float dual_mean(const VgDualParams& p, size_t i) {
+    return ((p.v.colour[i] + p.colour_b[i]) * 0.5f) / fmaxf(p.v.albedo[i], ALBEDO_FLOOR);
+}
+__device__ __forceinline__ float dual_diff(const VgDualParams& p, size_t i) {
+    return (p.v.colour[i] - p.colour_b[i]) / fmaxf(p.v.albedo[i], ALBEDO_FLOOR);
+}
+
+// The moments kernel's tile, staging and LDS layout (32 x 8 outputs, halo 3, 38 x 14 slots of one word and one
+// 16-byte guide record, 10 640 B; consecutive lanes read consecutive words / records at every tap: no bank
+// conflict), with another word: delta^2, delta = lum((A - B) / a) / 2, three divisions per slot, both colour
+// buffers and the albedo read once per slot.  E[delta^2] is the variance of lum(D_0) for independent halves, so
+// the word is a one-sample estimate of the noise alone and the 49 guide-weighted taps pool it: one weighted sum
+// (no first moment to subtract, no shift by the centre), and no luminance in the weight, since an edge of the
+// image is no evidence of noise.  Each lane sums its taps in one fixed order, rows not unrolled, the 7 taps of a
+// row unrolled; no atomics, plain vector stores.  A == B gives delta = 0 in every slot and Var_0 = 0 exactly.
+__global__ void __launch_bounds__(THREADS) vg_dual_kernel(const VgDualParams p) {
+    __shared__ float4 sg[VPIX];
+    __shared__ float sd[VPIX];
+    const VgParams& f = p.v;
+    const int W = (int)f.width, H = (int)f.height;
+    const int tx0 = (int)blockIdx.x * TW, ty0 = (int)blockIdx.y * TH;
+    const int tid = (int)threadIdx.x;
+    vg_stage_words(f, sg, sd, tx0, ty0, tid, [&](size_t a) {
+        const float d = 0.5f * lum(dual_diff(p, 3 * a), dual_diff(p, 3 * a + 1), dual_diff(p, 3 * a + 2));
+        return d * d;
+    });
+    __syncthreads();
+    const int tx = tid % TW, ty = tid / TW;
+    const int px = tx0 + tx, py = ty0 + ty;
+    if (px >= W || py >= H) return;
+    const int cq = (ty + VR) * VW + tx + VR;
+    const float4 gp = sg[cq];
+    float sw = 0.0f, s2 = 0.0f;
+#pragma unroll 1
+    for (int dy = -VR; dy <= VR; ++dy) {
+        const bool oky = in_range(py + dy, H);
+#pragma unroll
+        for (int dx = -VR; dx <= VR; ++dx) {
+            const bool ok = oky && in_range(px + dx, W);
+            const int q = cq + dy * VW + dx;
+            const float4 gq = sg[q];
+            const float n0 = gp.x - gq.x, n1 = gp.y - gq.y, n2 = gp.z - gq.z, dz = gp.w - gq.w;
+            const float e = (n0 * n0 + n1 * n1 + n2 * n2) * f.kn + dz * dz * f.kz;
+            const float w = ok ? __builtin_amdgcn_exp2f(-e) : 0.0f;
+            sw += w;
+            s2 += w * sd[q];
+        }
+    }
+    // (the centre tap has w = 1: sw >= 1)
+    const size_t pix = (size_t)py * f.width + (size_t)px;
+    // the lane's own D_0 from memory: the lines the staging loop just read
+    f.rout[pix] = make_float4(dual_mean(p, 3 * pix), dual_mean(p, 3 * pix + 1), dual_mean(p, 3 * pix + 2), s2 / sw);
+    f.gout[pix] = gp;
 }
 
 // One pass: atrous_kernel's tile (lattice pitch g, taps T points apart, halo 2 T points) over 16-byte
@@ -526,13 +601,12 @@ void enqueue_vg_passes(VgParams p, uint32_t iterations, float4* const* chain, hi
     }
 }
 
-}  // namespace
-
-// The moments kernel reads the caller's colour and no pass does (the last one reads the albedo), so
-// out == colour needs no copy for any K.
-void gpu_denoise_vg(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
-                    uint32_t width, uint32_t rows, uint32_t iterations, float sigma_luminance, float sigma_normal,
-                    float sigma_depth, float* out, float* out_variance, void* stream_ptr) {
+// The chain of the two single-frame entry points on the scratch: first(p, grid, stream) launches the kernel that
+// writes (D_0, Var_0) and the guide records, then the K passes ping-pong.
+template <class F>
+void vg_chain(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
+              uint32_t width, uint32_t rows, uint32_t iterations, float sigma_luminance, float sigma_normal,
+              float sigma_depth, float* out, float* out_variance, void* stream_ptr, const char* what, F&& first) {
     const size_t pixels = (size_t)width * rows;
     if (!s || s->pixels < pixels || s->rec_bytes < sizeof(float4)) throw std::runtime_error("denoise scratch too small");
     hipStream_t stream = (hipStream_t)stream_ptr;
@@ -546,9 +620,34 @@ void gpu_denoise_vg(DenoiseScratch* s, const float* colour, const float* albedo,
     p.rout = b0;
     p.gin = s->guides;
     p.gout = s->guides;
-    hipLaunchKernelGGL(vg_moments_kernel, dim3((width + TW - 1) / TW, (rows + TH - 1) / TH), dim3(THREADS), 0, stream, p);
+    first(p, dim3((width + TW - 1) / TW, (rows + TH - 1) / TH), stream);
     enqueue_vg_passes(p, iterations, chain, stream);
-    check(hipGetLastError(), "denoise_vg launch");
+    check(hipGetLastError(), what);
+}
+
+}  // namespace
+
+// The moments kernel reads the caller's colour and no pass does (the last one reads the albedo), so
+// out == colour needs no copy for any K.
+void gpu_denoise_vg(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
+                    uint32_t width, uint32_t rows, uint32_t iterations, float sigma_luminance, float sigma_normal,
+                    float sigma_depth, float* out, float* out_variance, void* stream_ptr) {
+    vg_chain(s, colour, albedo, normal, depth, width, rows, iterations, sigma_luminance, sigma_normal, sigma_depth, out,
+             out_variance, stream_ptr, "denoise_vg launch", [](const VgParams& p, dim3 grid, hipStream_t stream) {
+                 hipLaunchKernelGGL(vg_moments_kernel, grid, dim3(THREADS), 0, stream, p);
+             });
+}
+
+// Likewise the dual kernel is the only reader of the two colour buffers: out may be either, for any K.
+void gpu_denoise_vg_dual(DenoiseScratch* s, const float* colour_a, const float* colour_b, const float* albedo,
+                         const float* normal, const float* depth, uint32_t width, uint32_t rows, uint32_t iterations,
+                         float sigma_luminance, float sigma_normal, float sigma_depth, float* out, float* out_variance,
+                         void* stream_ptr) {
+    vg_chain(s, colour_a, albedo, normal, depth, width, rows, iterations, sigma_luminance, sigma_normal, sigma_depth,
+             out, out_variance, stream_ptr, "denoise_vg_dual launch",
+             [colour_b](const VgParams& p, dim3 grid, hipStream_t stream) {
+                 hipLaunchKernelGGL(vg_dual_kernel, grid, dim3(THREADS), 0, stream, VgDualParams{p, colour_b});
+             });
 }
 
 // ---- temporal accumulation (SVGF's temporal half): one kernel in the moments kernel's place, then

@@ -66,6 +66,12 @@ void gpu_denoise(DenoiseScratch* s, const float* colour, const float* albedo, co
 void gpu_denoise_vg(DenoiseScratch* s, const float* colour, const float* albedo, const float* normal, const float* depth,
                     uint32_t width, uint32_t rows, uint32_t iterations, float sigma_luminance, float sigma_normal,
                     float sigma_depth, float* out, float* out_variance, void* stream);
+// The same chain with the variance taken from two frames of one camera over disjoint sample windows (vg_dual_kernel in
+// the moments kernel's place); out may be either colour buffer.
+void gpu_denoise_vg_dual(DenoiseScratch* s, const float* colour_a, const float* colour_b, const float* albedo,
+                         const float* normal, const float* depth, uint32_t width, uint32_t rows, uint32_t iterations,
+                         float sigma_luminance, float sigma_normal, float sigma_depth, float* out, float* out_variance,
+                         void* stream);
 // Temporal accumulation in front of the variance-guided passes (denoise.hip).  A History holds the
 // previous frame's camera, guide records, colour history, luminance moments and history length for
 // width x rows pixels, plus the work buffers of the passes: 112 B per pixel, allocated on `device`

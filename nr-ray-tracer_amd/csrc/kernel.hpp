@@ -1204,6 +1204,9 @@ struct ShadeSig {
     static constexpr bool has(uint32_t kind) { return ((MATS >> kind) & 1u) != 0u; }
     static constexpr bool cam_fixed = (CAM & SHADE_CAM_RUNTIME) == 0u;
     static constexpr bool defocus = (CAM & SHADE_DEFOCUS) != 0u, multi = (CAM & SHADE_MULTI) != 0u;
+    // the claim adds RenderParams::sample0: the generic kernels always, a specialised one when its launch's
+    // window starts past 0 (a window at 0 compiles to the loop without the offset)
+    static constexpr bool window = !cam_fixed || (CAM & SHADE_WINDOW) != 0u;
 };
 using ShadeAny = ShadeSig<0xFFFFFFFFu, SHADE_CAM_RUNTIME>;
 
@@ -3673,7 +3676,7 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             for (uint32_t l = lane; l < nf; l += 64u) o[l] = (float)((a[l] * p.acc_unscale) / spp);
         };
 
-        uint32_t slot = 0, j = 0, cur = 0;  // ring slot, pixel in the group, sample index of this lane's path
+        uint32_t slot = 0, j = 0, cur = 0;  // ring slot, pixel in the group, sample index (of the pixel: sample0 + the launch's) of this lane's path
         uint32_t pxy = 0;                   // this path's pixel, x | y << 16
         bool alive = false;                 // the lane holds a path
         bool killed = false;                // absorbed by a metal (or padding): black, ends at the next shading step
@@ -3828,6 +3831,7 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
                     const uint32_t idx = second ? claim - GS : claim;
                     j = idx & (P - 1u);
                     cur = idx >> logP;
+                    if constexpr (SHADE::window) cur += p.sample0;  // once per claim: `cur` only keys the blocks
                     pxy = slot_xy[slot * P + j];
                 }
             }

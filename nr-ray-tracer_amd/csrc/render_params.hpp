@@ -24,8 +24,9 @@ namespace dev {
 // texture is a solid colour or a PAL16 image (scene-specialised kernels only) (kernel.hpp).
 constexpr int KF_PROF = 1, KF_PERLIN = 2, KF_FLAT = 4, KF_PLANES = 8, KF_TEXPAL = 16;
 // Camera-mode bits of a scene-specialised kernel's shading signature (kernel.hpp ShadeSig<MATS, CAM>):
-// a non-zero defocus disk, spp > 1, or the mode read from RenderParams at run time.
-constexpr uint32_t SHADE_DEFOCUS = 1u, SHADE_MULTI = 2u, SHADE_CAM_RUNTIME = 4u;
+// a non-zero defocus disk, spp > 1, or the mode read from RenderParams at run time; SHADE_WINDOW: the launch's
+// sample window starts past 0 (RenderParams::sample0: without the bit the kernel never reads it).
+constexpr uint32_t SHADE_DEFOCUS = 1u, SHADE_MULTI = 2u, SHADE_CAM_RUNTIME = 4u, SHADE_WINDOW = 8u;
 // Exact kernel, small scenes: at most this many slots of the culling tree are tested in slot order
 // instead of walked (EXACT_SIG_SLOTS / EXACT_SIG_SLOTS_PF; host default and launcher share it)
 constexpr uint32_t EXACT_SLOTS_MAX = 32;
@@ -101,6 +102,10 @@ struct RenderParams {
     // next launch fills: nrt_render_device); nrt_render, a one-shot call, asks for 16 (smaller last
     // groups shorten a lone launch's tail)
     uint32_t groups_per_wave;
+    // Philox: the launch's sample window starts here (nrt_render_opts.sample_offset): sample `cur` of the
+    // launch's spp draws the blocks of sample index sample0 + cur (kernel.hpp, where a lane claims its sample;
+    // a scene-specialised kernel reads it only when its signature has SHADE_WINDOW)
+    uint32_t sample0;
 };
 
 }  // namespace nrt

@@ -62,7 +62,7 @@ class _Camera(C.Structure):
 
 class _RenderOpts(C.Structure):
     _fields_ = [("precision", C.c_uint32), ("rng", C.c_uint32), ("device", C.c_int32), ("row_offset", C.c_uint32),
-                ("row_stride", C.c_uint32), ("trace", C.c_uint32), ("gpus", C.c_uint32), ("reserved", C.c_uint32)]
+                ("row_stride", C.c_uint32), ("trace", C.c_uint32), ("gpus", C.c_uint32), ("sample_offset", C.c_uint32)]
 
 
 class _SceneStats(C.Structure):
@@ -149,6 +149,10 @@ SIGNATURES = {
                                  C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nrt_denoise_vg_device": (C.c_int, [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseVgOpts), C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrt_denoise_vg_dual": (C.c_int, [C.POINTER(C.c_float)] * 5 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseVgOpts),
+                                      C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nrt_denoise_vg_dual_device": (C.c_int, [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseVgOpts),
+                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrt_history_new": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_int32]),
     "nrt_history_free": (None, [C.c_void_p]),
     "nrt_history_reset": (C.c_int, [C.c_void_p]),
@@ -375,7 +379,7 @@ class CameraBuilder:
 
 
 def _opts(precision: str, rng: str, device: int, row_offset: int, row_stride: int,
-          trace: str = "auto", gpus: int = 0) -> _RenderOpts:
+          trace: str = "auto", gpus: int = 0, sample_offset: int = 0) -> _RenderOpts:
     if precision not in PRECISION:
         raise ValueError(f"precision must be one of {list(PRECISION)}")
     if rng not in RNG:
@@ -386,6 +390,9 @@ def _opts(precision: str, rng: str, device: int, row_offset: int, row_stride: in
     o.precision, o.rng, o.device = PRECISION[precision], RNG[rng], device
     o.row_offset, o.row_stride, o.trace = row_offset, row_stride, TRACE[trace]
     o.gpus = gpus
+    if not 0 <= sample_offset < 1 << 32:
+        raise NrtError(-1, f"sample_offset {sample_offset} is not in 0 .. 2^32 - 1")
+    o.sample_offset = sample_offset
     return o
 
 
@@ -441,30 +448,50 @@ class Scene:
     def render(self, camera: Optional[Camera] = None, precision: str = "f64", rng: str = "chacha8",
                device: int = -1, row_offset: int = 0, row_stride: int = 1,
                progress: Optional[Callable[[int], None]] = None, trace: str = "auto", gpus: int = 0,
-               denoise=False) -> np.ndarray:
+               denoise=False, sample_offset: int = 0, variance_out: Optional[np.ndarray] = None) -> np.ndarray:
         """Camera::render -> Rgb32FImage as float32 array (rows, W, 3).  gpus = N >= 1: the whole frame
         over devices device .. device+N-1 (device -1: 0), one RCCL gather (nrt_render_opts.gpus).
+        sample_offset = s0 (rng "philox"): samples s0 .. s0 + spp - 1 of every pixel instead of 0 .. spp - 1
+        (nrt_render_opts.sample_offset): frames of disjoint windows have independent noise.
         denoise = True (or the number of passes, 1..5): the frame, then its feature buffers
         (render_aov), then the a-trous filter (nrt.denoise) over both; whole frames on one device.
         denoise = "variance": the same chain with the variance-guided filter (nrt.denoise_vg).
-        denoise = a History: the same chain with History.denoise and this camera, frame after frame."""
+        denoise = "dual": the windows [s0, s0 + spp/2) and [s0 + spp/2, s0 + spp) as two frames, the feature
+        buffers, then nrt.denoise_vg_dual: the frame over the same spp samples as the undenoised render, its
+        variance measured between the halves (an even spp >= 4, so that each half jitters).
+        denoise = a History: the same chain with History.denoise and this camera, frame after frame; live
+        frames of a sequence need sample_offset = k * spp at frame k, or every frame of a still camera
+        carries the same noise and the history averages nothing away.
+        variance_out (denoise "variance", "dual" or a History): a (rows, W) float32 array for the filtered
+        variance."""
         cam = camera or self.camera
         if cam is None:
             raise ValueError("no camera")
-        if isinstance(denoise, str) and denoise != "variance":
-            raise ValueError(f"denoise must be False, True, 1..5, 'variance' or a History, not {denoise!r}")
+        if isinstance(denoise, str) and denoise not in ("variance", "dual"):
+            raise ValueError(f"denoise must be False, True, 1..5, 'variance', 'dual' or a History, not {denoise!r}")
+        if variance_out is not None and not (isinstance(denoise, History) or denoise in ("variance", "dual")):
+            raise ValueError("variance_out needs denoise = 'variance', 'dual' or a History")
         if denoise:
             if row_stride > 1 or row_offset:
                 raise ValueError("denoise filters whole frames: row_offset 0 and row_stride 1")
-            frame = self.render(cam, precision, rng, device, progress=progress, trace=trace, gpus=gpus)
+            kw = dict(precision=precision, rng=rng, device=device, progress=progress, trace=trace, gpus=gpus)
+            if denoise == "dual":
+                half = cam.samples_per_pixel // 2
+                if cam.samples_per_pixel % 2 or half < 2:
+                    raise NrtError(-1, f"denoise='dual' halves the samples: samples_per_pixel must be even and >= 4 "
+                                       f"(each half jitters), not {cam.samples_per_pixel}")
+                a, b = (self.render(cam.with_samples(half), sample_offset=sample_offset + k * half, **kw) for k in (0, 1))
+                aov = self.render_aov(cam, trace=trace, device=device)
+                return denoise_vg_dual(a, b, device=device, out=a, variance_out=variance_out, **aov)
+            frame = self.render(cam, sample_offset=sample_offset, **kw)
             aov = self.render_aov(cam, trace=trace, device=device)
             if isinstance(denoise, History):
-                return denoise.denoise(frame, camera=cam, out=frame, **aov)
+                return denoise.denoise(frame, camera=cam, out=frame, variance_out=variance_out, **aov)
             if denoise == "variance":
-                return denoise_vg(frame, device=device, out=frame, **aov)
+                return denoise_vg(frame, device=device, out=frame, variance_out=variance_out, **aov)
             return globals()["denoise"](frame, iterations=5 if denoise is True else int(denoise), device=device,
                                         out=frame, **aov)
-        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus)
+        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset)
         rows = lib().nrt_rows_selected(cam.height, C.byref(o))
         out = np.empty((rows, cam.width, 3), dtype=np.float32)
         cb = PROGRESS_FN(lambda _u, n: progress(n)) if progress else PROGRESS_FN()
@@ -520,6 +547,18 @@ class Scene:
                                            C.c_void_p(normal_ptr), C.c_void_p(depth_ptr), width, rows, C.byref(d),
                                            device, C.c_void_p(out_ptr), C.c_void_p(variance_ptr), C.c_void_p(stream)))
 
+    def denoise_vg_dual_device(self, colour_a_ptr: int, colour_b_ptr: int, albedo_ptr: int, normal_ptr: int,
+                               depth_ptr: int, width: int, rows: int, out_ptr: int, variance_ptr: int = 0,
+                               iterations: int = 5, sigma_luminance: float = 4.0, sigma_normal: float = 0.3,
+                               sigma_depth: float = 0.5, device: int = -1, stream: int = 0) -> None:
+        """Enqueue the dual-buffer variance-guided filter over device memory (nrt_denoise_vg_dual_device; the
+        scene's variance-guided scratch); out_ptr may be either colour pointer, variance_ptr may be 0."""
+        d = _DenoiseVgOpts(iterations, sigma_luminance, sigma_normal, sigma_depth)
+        _check(lib().nrt_denoise_vg_dual_device(self._h, C.c_void_p(colour_a_ptr), C.c_void_p(colour_b_ptr),
+                                                C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr), C.c_void_p(depth_ptr),
+                                                width, rows, C.byref(d), device, C.c_void_p(out_ptr),
+                                                C.c_void_p(variance_ptr), C.c_void_p(stream)))
+
     def phase_profile(self, camera: Optional[Camera] = None, precision: str = "f32", rng: str = "philox",
                       device: int = -1, trace: str = "auto") -> dict:
         """Diagnostic render with per-wave stamps: cycle shares of camera / trace / shading."""
@@ -551,21 +590,22 @@ class Scene:
 
     def render_device(self, out_ptr: int, out_len: int, camera: Optional[Camera] = None, precision: str = "f32",
                       rng: str = "philox", device: int = -1, row_offset: int = 0, row_stride: int = 1,
-                      stream: int = 0, trace: str = "auto", gpus: int = 0) -> None:
+                      stream: int = 0, trace: str = "auto", gpus: int = 0, sample_offset: int = 0) -> None:
         """Enqueue a render into device memory (e.g. a torch tensor's data_ptr) on a HIP stream; gpus = N
-        >= 1: the whole frame over N devices into out_ptr on the first (nrt_render_opts.gpus)."""
+        >= 1: the whole frame over N devices into out_ptr on the first (nrt_render_opts.gpus); sample_offset
+        as in render."""
         cam = camera or self.camera
-        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus)
+        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset)
         _check(lib().nrt_render_device(self._h, C.byref(cam._c()), C.byref(o), C.c_void_p(out_ptr), out_len,
                                        C.c_void_p(stream)))
 
 
     def prepare(self, camera: Optional[Camera] = None, precision: str = "f32", rng: str = "philox",
-                device: int = -1, trace: str = "auto", gpus: int = 0) -> None:
+                device: int = -1, trace: str = "auto", gpus: int = 0, sample_offset: int = 0) -> None:
         """nrt_render_prepare: the uploads and, with gpus = N >= 1, the RCCL communicators and shard
         buffers of such a render, done now (NrtError code -4 when librccl cannot gather)."""
         cam = camera or self.camera
-        o = _opts(precision, rng, device, 0, 1, trace, gpus)
+        o = _opts(precision, rng, device, 0, 1, trace, gpus, sample_offset)
         _check(lib().nrt_render_prepare(self._h, C.byref(cam._c()), C.byref(o)))
 
     def render_timings(self) -> dict:
@@ -722,6 +762,24 @@ def denoise_vg(colour: np.ndarray, albedo: np.ndarray, normal: np.ndarray, depth
     (c, _, _, _, out, _), p = _frame_args("denoise_vg", "colour", colour, albedo, normal, depth, out, variance_out)
     d = _DenoiseVgOpts(iterations, sigma_luminance, sigma_normal, sigma_depth)
     _check(lib().nrt_denoise_vg(*p[:4], c.shape[1], c.shape[0], C.byref(d), device, p[4], p[5]))
+    return out
+
+
+def denoise_vg_dual(frame_a: np.ndarray, frame_b: np.ndarray, albedo: np.ndarray, normal: np.ndarray,
+                    depth: np.ndarray, iterations: int = 5, sigma_luminance: float = 4.0, sigma_normal: float = 0.3,
+                    sigma_depth: float = 0.5, device: int = -1, out: Optional[np.ndarray] = None,
+                    variance_out: Optional[np.ndarray] = None) -> np.ndarray:
+    """Variance-guided a-trous filter with a dual-buffer variance (nrt_denoise_vg_dual): frame_a and frame_b are two
+    (rows, W, 3) frames of one camera over disjoint sample windows of equal length (Scene.render's sample_offset); the
+    filtered frame is that of their mean, the variance is measured between them.  Other arguments as `denoise_vg`;
+    `out` may be either frame."""
+    (c, _, _, _, out, _), p = _frame_args("denoise_vg_dual", "frame_a", frame_a, albedo, normal, depth, out, variance_out)
+    b = frame_b if frame_b.dtype == np.float32 and frame_b.flags.c_contiguous else np.ascontiguousarray(frame_b, np.float32)
+    if b.shape != c.shape:
+        raise NrtError(-1, f"denoise_vg_dual: frame_b {b.shape} is not frame_a's {c.shape}")
+    d = _DenoiseVgOpts(iterations, sigma_luminance, sigma_normal, sigma_depth)
+    _check(lib().nrt_denoise_vg_dual(p[0], b.ctypes.data_as(C.POINTER(C.c_float)), *p[1:4], c.shape[1], c.shape[0],
+                                     C.byref(d), device, p[4], p[5]))
     return out
 
 
