@@ -96,6 +96,21 @@ constexpr int BLOCK = NRT_BLOCK;
 #define NRT_PK_QUAD 1  // ... quads (axis and general), triangles and boxes: packed (quads.toml, five axis quads,
                        // 1024^2 spp 64: 0.760 ms packed, 0.827 unpacked)
 #endif
+// Scalar-pipe savings of the Philox loop and the world-list unit tests (each decides and rounds as the
+// form it replaces, for every input; 0 restores that form for A/B runs):
+#ifndef NRT_BOOK_GUARD
+#define NRT_BOOK_GUARD 1  // the loop head's flush / fetch / exit tests behind one wave-uniform test of their
+                          // shared precondition (a full slot, or fewer than NRT_FETCH_AHEAD samples to claim)
+#endif
+#ifndef NRT_DONES_SUM
+#define NRT_DONES_SUM 1  // completion counts: one ballot of `ends` and one per slot after the first
+#endif
+#ifndef NRT_CONTRIB_BITS
+#define NRT_CONTRIB_BITS 1  // "some component of contrib is not +-0" from the three words' OR, one compare
+#endif
+#ifndef NRT_QUAD_HI_FOLD
+#define NRT_QUAD_HI_FOLD 1  // quads: alpha <= 1 & beta <= 1 as max(alpha, beta) <= 1 (as min >= 0 already is)
+#endif
 #ifndef NRT_BOX_DEFER
 // world list: 1 = a box unit's (PRIM_BOX / PRIM_BOXY) face is resolved once, for the winner of the whole
 // run loop, instead of per unit and ray (the unit keeps (t, its index, entry / exit)).  Measured on C5
@@ -909,8 +924,17 @@ __device__ __forceinline__ void axis_quad_run(ConstPrimWorld<float> wp, uint32_t
                           q->AB[2 * A1 + 1] * p1 + q->AB[2 * A2 + 1] * p2 - q->AB[7]};
 #endif
         const float lo = fminf(ab.x, ab.y);
+#if NRT_QUAD_HI_FOLD
+        // max <= 1 decides as (alpha <= 1) & (beta <= 1) for every non-NaN pair, as min >= 0 does for the
+        // lower edge (one mask AND less).  A NaN coordinate can only come from a rejected denominator or t:
+        // alpha and beta are finite sums of o + t d, NaN only with t NaN (fails t >= 0.001) or t infinite,
+        // which needs 1/d_a infinite, d_a = 0, rejected by the first term
+        const bool ok = (fabsf(d[A]) >= q->N[A2]) & (t >= 0.001f) & (t <= t_best) & (lo >= 0.0f) &
+                        (fmaxf(ab.x, ab.y) <= 1.0f);
+#else
         const bool ok = (fabsf(d[A]) >= q->N[A2]) & (t >= 0.001f) & (t <= t_best) & (lo >= 0.0f) & (ab.x <= 1.0f) &
                         (ab.y <= 1.0f);
+#endif
         t_best = ok ? t : t_best;
         best = ok ? (int32_t)k : best;
     }
@@ -1129,7 +1153,11 @@ __device__ __forceinline__ void world_run(ConstPrimWorld<float> wp, uint32_t kin
         const float lo = fminf(ab.x, ab.y);
         // quad closed [0,1]^2 (plane.rs:121-126), triangle open (plane.rs:128-133); a NaN
         // coordinate can only come from a rejected denominator or t
+#if NRT_QUAD_HI_FOLD  // (max <= 1: as in axis_quad_run; the denominator term rejects |N.d| < 1e-8, NaN included)
+        const bool inside = quad ? (lo >= 0.0f) & (fmaxf(ab.x, ab.y) <= 1.0f) : (lo > 0.0f) & (ab.x + ab.y < 1.0f);
+#else
         const bool inside = quad ? (lo >= 0.0f) & (ab.x <= 1.0f) & (ab.y <= 1.0f) : (lo > 0.0f) & (ab.x + ab.y < 1.0f);
+#endif
         const bool ok = (fabsf(dn.x) >= 1e-8f) & (t >= 0.001f) & (t <= t_best) & inside;
         t_best = ok ? t : t_best;
         best = ok ? (int32_t)k : best;
@@ -3589,11 +3617,13 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
         double* acc = (double*)(lds + ring_bytes) + wv * NS * P * 3u;
         uint32_t* slot_xy = (uint32_t*)(lds + ring_bytes + (BLOCK / 64) * NS * P * 3u * sizeof(double)) + wv * NS * P;
         constexpr uint32_t NO_GROUP = 0xFFFFFFFFu, PAD_XY = 0xFFFFFFFFu;
-        uint32_t gids[NS], dones[NS];  // group held by each slot and its finished samples (wave-uniform)
+        // group held by each slot and its samples not yet finished (wave-uniform; GS for an empty slot, so 0
+        // means "a group to write out" and nothing else)
+        uint32_t gids[NS], todo[NS];
 #pragma unroll
         for (uint32_t k = 0; k < NS; ++k) {
             gids[k] = NO_GROUP;
-            dones[k] = 0;
+            todo[k] = GS;
         }
         uint32_t cs = 0, next = GS;                 // claiming from slot cs at index next
         bool ready = false;                         // slot (cs + 1) % NS holds a group not yet claimed from
@@ -3659,7 +3689,7 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
 #pragma unroll
             for (uint32_t k = 0; k < NS; ++k) {
                 gids[k] = k == r ? gid : gids[k];
-                dones[k] = k == r ? 0u : dones[k];
+                todo[k] = k == r ? GS : todo[k];
             }
             ready = true;
         };
@@ -3729,23 +3759,41 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             // Group bookkeeping at the loop head, where little state is live: write out
             // finished groups, and take the next group into the free slot as soon as
             // fewer than a wave's worth of samples are left to claim.
+            // Each of the three steps needs a finished group (todo[k] == 0) or fewer than NRT_FETCH_AHEAD
+            // samples left to claim (the exit needs none left): in the iterations between two group
+            // boundaries neither holds, and one wave-uniform test of that skips all three unchanged.
+            // (As integers: the least of the slots' unfinished counts and the claimable samples in units of
+            // NRT_FETCH_AHEAD is 0; compares joined by ORs cost the scalar unit twice as much.)
+            uint32_t quiet = 0;
+            if constexpr (NRT_BOOK_GUARD) {
+                quiet = (GS - next) / NRT_FETCH_AHEAD;
 #pragma unroll
-            for (uint32_t k = 0; k < NS; ++k) {
-                if (gids[k] != NO_GROUP && dones[k] == GS) {
-                    flush(gids[k], k);
-                    gids[k] = NO_GROUP;
+                for (uint32_t k = 0; k < NS; ++k) {
+                    quiet = min(quiet, todo[k]);
+                    asm volatile("" : "+s"(quiet));  // (kept in an SGPR: a three-way minimum would go to the VALU)
                 }
             }
-            if constexpr (NS == 2) {
-                if (!exhausted && !ready && GS - next < NRT_FETCH_AHEAD && (cs ? gids[0] : gids[1]) == NO_GROUP) fetch(cs ^ 1u);
-            } else if (!exhausted && !ready && GS - next < NRT_FETCH_AHEAD) {
-                const uint32_t r = (cs + 1u) & (NS - 1u);
-                bool free = false;
+            if (quiet == 0u) {
 #pragma unroll
-                for (uint32_t k = 0; k < NS; ++k) free |= k == r && gids[k] == NO_GROUP;
-                if (free) fetch(r);
+                for (uint32_t k = 0; k < NS; ++k) {
+                    if (todo[k] == 0u && gids[k] != NO_GROUP) {  // (an empty slot's count is GS)
+                        flush(gids[k], k);
+                        gids[k] = NO_GROUP;
+                        todo[k] = GS;
+                    }
+                }
+                if constexpr (NS == 2) {
+                    if (!exhausted && !ready && GS - next < NRT_FETCH_AHEAD && (cs ? gids[0] : gids[1]) == NO_GROUP)
+                        fetch(cs ^ 1u);
+                } else if (!exhausted && !ready && GS - next < NRT_FETCH_AHEAD) {
+                    const uint32_t r = (cs + 1u) & (NS - 1u);
+                    bool free = false;
+#pragma unroll
+                    for (uint32_t k = 0; k < NS; ++k) free |= k == r && gids[k] == NO_GROUP;
+                    if (free) fetch(r);
+                }
+                if (exhausted && !ready && GS - next == 0u && __ballot(alive) == 0ull) break;
             }
-            if (exhausted && !ready && GS - next == 0u && __ballot(alive) == 0ull) break;
             if constexpr (SETPRIO > 0) __builtin_amdgcn_s_setprio(0);
             const unsigned long long t0 = stamp();
             HitMin<R, MAXD> hm;
@@ -3793,7 +3841,16 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
 
             // finished samples: radiance into the pixel's LDS sum, completion counts per slot
             const bool ends = sh && !scatter;
-            if (ends && (contrib.x != R(0) || contrib.y != R(0) || contrib.z != R(0))) {
+            auto lit = [&]() {  // some component is not +-0 (a NaN counts, as with !=)
+                if constexpr (NRT_CONTRIB_BITS && sizeof(R) == 4) {
+                    // every bit below the sign, of the three words at once: one compare instead of three and two ORs
+                    return ((__float_as_uint((float)contrib.x) | __float_as_uint((float)contrib.y) |
+                             __float_as_uint((float)contrib.z)) << 1) != 0u;
+                } else {
+                    return contrib.x != R(0) || contrib.y != R(0) || contrib.z != R(0);
+                }
+            };
+            if (ends && lit()) {
                 double* a = acc + (slot * P + j) * 3u;
                 if constexpr (sizeof(R) == 4) {  // 2^k scaling and rint exact in f32 (host: k in range)
                     atomicAdd(a, (double)__builtin_rintf(contrib.x * p.acc_scale_f));
@@ -3805,8 +3862,21 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
                     atomicAdd(a + 2, rint((double)contrib.z * p.acc_scale));
                 }
             }
+#if NRT_DONES_SUM
+            {  // slot 0's count is what the other slots leave of the wave's (a lane's slot is < NS)
+                uint32_t d0 = (uint32_t)__popcll(__ballot(ends));
 #pragma unroll
-            for (uint32_t k = 0; k < NS; ++k) dones[k] += (uint32_t)__popcll(__ballot(ends && slot == k));
+                for (uint32_t k = 1; k < NS; ++k) {
+                    const uint32_t dk = (uint32_t)__popcll(__ballot(ends && slot == k));
+                    todo[k] -= dk;
+                    d0 -= dk;
+                }
+                todo[0] -= d0;
+            }
+#else
+#pragma unroll
+            for (uint32_t k = 0; k < NS; ++k) todo[k] -= (uint32_t)__popcll(__ballot(ends && slot == k));
+#endif
 
             // lanes without a path claim the next samples, in lane order: slot cs from
             // `next`, then the group waiting in slot (cs + 1) % NS

@@ -2,9 +2,11 @@
 
 usage: python scripts/asm_stats.py [--exact] [mangled-name fragment] [-DFLAG ...]
        python scripts/asm_stats.py --targs "float, nrt::dev::Philox, -1, false, false, 4, nrt::dev::BvhSig<4, false>"
+       python scripts/asm_stats.py --asm kernel.s
 default fragment: the headline kernel (f32, Philox, world list, LDS scene, KF_FLAT) of kernels_fast.hip.
 --targs: the template arguments of a scene-specialised kernel (jit.hip builds them with hiprtc; the
 bench line's `pmc.kernel` names them), instantiated here with hipcc and the JIT's flags.
+--asm: no compile; the loop reports (VALU classes, scalar-pipe families) of a kernel's assembly already in a file.
 Writes the kernel's assembly to /tmp/nrt_kernel.s and prints VGPR / SGPR / spill / occupancy figures.
 """
 import collections
@@ -22,6 +24,11 @@ FLAGS = ["-std=c++17", "-O3", "-fPIC", "-fno-fast-math", "-Wno-unused-function",
 
 def main():
     args = sys.argv[1:]
+    if args and args[0] == "--asm":
+        body = open(args[1]).read()
+        loop_classes(body)
+        loop_scalar(body)
+        return
     pkg = os.path.join(ROOT, "nr-ray-tracer_amd")
     inc = ["-I" + os.path.join(pkg, "csrc"), "-I" + os.path.join(ROOT, "include")]
     td = tempfile.mkdtemp()
@@ -63,6 +70,7 @@ def main():
     print(f"{m.group(1)[:90]}\ninstructions {len(ins)}  valu {valu}  salu/branch {salu}")
     print("  ".join(f"{k} {n}" for k, n in c.most_common(30)))
     loop_classes(body)
+    loop_scalar(body)
     # kernel-resource-usage remarks of this kernel (VGPRs, SGPRs, spills, scratch, occupancy)
     lines = r.stderr.split("\n")
     for k, line in enumerate(lines):
@@ -84,13 +92,12 @@ CLASSES = [("TRANS_F32", r"^v_(rcp|rsq|sqrt|exp|log|sin|cos)_(iflag_)?f32"), ("T
                      r"bitop3|perm|add3|lshl_add|lshl_or|and_or|or3|xad|min_u32|max_u32|min_i32|max_i32|bcnt|mbcnt)\w*")]
 
 
-def loop_classes(body):
-    """Static VALU mix of the kernel's outermost loop (first `Loop Header: Depth=1` block to its last
-    back-edge), in rocprofv3's SQ_INSTS_VALU_* classes, with OTHER broken down by opcode: what the
-    profile's valu_mix OTHER share is made of (compares, selects, moves, min/max, lane moves)."""
+def outer_loop(body):
+    """(lines, head, tail) of the kernel's largest outermost loop: a `Loop Header: Depth=1` block to its last
+    back-edge (the staging loops before the render loop are small); head None when there is no loop."""
     lines = body.split("\n")
     best = None
-    for head, l in enumerate(lines):  # the largest outermost loop (the staging loops before it are small)
+    for head, l in enumerate(lines):
         if "Loop Header: Depth=1" not in l:
             continue
         label = l.split(":")[0].strip()
@@ -98,11 +105,26 @@ def loop_classes(body):
                    default=None)
         if tail is not None and tail > head and (best is None or tail - head > best[1] - best[0]):
             best = (head, tail)
-    if best is None:
+    return (lines, None, None) if best is None else (lines, best[0], best[1])
+
+
+def loop_instructions(lines, head, tail):
+    out = []
+    for l in lines[head:tail + 1]:
+        l = l.split(";")[0].strip()
+        if l and not l.startswith(".") and not l.endswith(":"):
+            out.append(l)
+    return out
+
+
+def loop_classes(body):
+    """Static VALU mix of the kernel's outermost loop (first `Loop Header: Depth=1` block to its last
+    back-edge), in rocprofv3's SQ_INSTS_VALU_* classes, with OTHER broken down by opcode: what the
+    profile's valu_mix OTHER share is made of (compares, selects, moves, min/max, lane moves)."""
+    lines, head, tail = outer_loop(body)
+    if head is None:
         return
-    head, tail = best
-    ops = [l.strip().split()[0] for l in lines[head:tail + 1]
-           if l.strip() and not l.strip().startswith((".", ";")) and not l.strip().endswith(":")]
+    ops = [l.split()[0] for l in loop_instructions(lines, head, tail)]
     valu = [o for o in ops if o.startswith("v_")]
     cls = collections.Counter()
     other = collections.Counter()
@@ -114,6 +136,50 @@ def loop_classes(body):
     print(f"outer loop (lines {head}-{tail}): {len(ops)} instructions, {len(valu)} VALU")
     print("  classes: " + "  ".join(f"{k} {n} ({n / len(valu):.0%})" for k, n in cls.most_common()))
     print("  OTHER:   " + "  ".join(f"{k} {n}" for k, n in other.most_common(16)))
+
+
+# The scalar pipe's share of the loop (what the profile counts as SQ_INSTS_SALU + SQ_INSTS_BRANCH +
+# SQ_INSTS_SMEM, and the waits that issue beside them), by broad family.  An instruction that writes the
+# exec mask is "exec" whatever its opcode; the first matching row below decides the rest; every scalar
+# instruction lands in exactly one family, so the counts add up to the total.
+SCALAR_FAMILIES = [("exec", r"^s_\w+_saveexec_b\d+$"),
+                   ("branch", r"^s_(c?branch\w*|setpc_b64|swappc_b64|call_b64|endpgm)$"),
+                   ("smem", r"^s_(buffer_)?load_\w+$"),
+                   ("wait", r"^s_(waitcnt\w*|nop|sleep|barrier|delay_alu|wait_\w+)$"),
+                   ("cmp_select", r"^s_(cmpk?_\w+|cselect_\w+|cmov\w*|bitcmp\w+)$"),
+                   ("bitcount", r"^s_(bcnt\d_\w+|ff[01]_\w+|flbit_\w+)$"),
+                   ("mask", r"^s_(and|or|xor|andn1|andn2|orn1|orn2|nand|nor|xnor|not)_b64$"),
+                   ("arith_move", r"^s_\w+$")]
+
+
+def scalar_families(insts):
+    """Counter of family -> count over the instruction lines `insts` (operands included); scalar-pipe
+    instructions only (s_*), vector and memory instructions are skipped."""
+    fam = collections.Counter()
+    for l in insts:
+        op, _, rest = l.partition(" ")
+        if not op.startswith("s_"):
+            continue
+        op = re.sub(r"_e(32|64)$", "", op)
+        dest = rest.split(",")[0].strip()
+        if dest in ("exec", "exec_lo", "exec_hi") and not re.match(SCALAR_FAMILIES[0][1], op):
+            fam["exec"] += 1
+            continue
+        fam[next(name for name, rx in SCALAR_FAMILIES if re.match(rx, op))] += 1
+    return fam
+
+
+def loop_scalar(body):
+    """Static scalar-pipe mix of the outermost loop, beside loop_classes' VALU mix."""
+    lines, head, tail = outer_loop(body)
+    if head is None:
+        return
+    insts = loop_instructions(lines, head, tail)
+    fam = scalar_families(insts)
+    total = sum(fam.values())
+    valu = sum(1 for l in insts if l.startswith("v_"))
+    print(f"outer loop scalar pipe: {total} instructions ({total / max(valu, 1):.2f} per VALU)")
+    print("  families: " + "  ".join(f"{name} {fam[name]}" for name, _ in SCALAR_FAMILIES))
 
 
 if __name__ == "__main__":

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <string>
 #include <vector>
 #include <algorithm>
 
@@ -86,6 +87,84 @@ __global__ void __launch_bounds__(256) bench(uint64_t* out, uint32_t* sink) {
     }
 }
 
+// Scalar instructions beside the vector stream: the same dependent-free v_fma_f32 chains with S 64-bit
+// scalar ANDs on private SGPR pairs spread evenly over every 8 FMAs (S = 0, 2, 4, 8: 0, 1:4, 1:2, 1:1),
+// at 8 waves per SIMD.  The four SIMDs of a CU share one scalar unit; if it takes one instruction per
+// cycle, the CU's 4 FMAs per cycle leave it free at 1:4 and short at 1:1, and a wave that issues a scalar
+// instruction may or may not leave its SIMD's vector slot of that cycle to another wave: the VALU
+// instructions per cycle per SIMD at each ratio say which.
+template <int S>
+__global__ void __launch_bounds__(256) bench_salu(uint64_t* out, uint32_t* sink) {
+    float acc[CHAINS];
+    const float b = 1.0f + (threadIdx.x + 7u) * 1e-7f;
+#pragma unroll
+    for (int c = 0; c < CHAINS; ++c) acc[c] = 1.0f + (threadIdx.x * CHAINS + c) * 1e-7f;
+    uint64_t m[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m[k] = ~0ull >> (blockIdx.x & 7u) >> k;  // wave-uniform: SGPR pairs
+    const uint64_t keep = ~0ull >> 16;
+    __syncthreads();
+    const uint64_t t0 = __builtin_amdgcn_s_memtime();
+    const uint64_t r0 = __builtin_amdgcn_s_memrealtime();
+    for (int it = 0; it < ITERS; ++it) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+#pragma unroll
+            for (int c = 0; c < CHAINS; ++c) {
+                asm volatile("v_fma_f32 %0, %1, %1, %0" : "+v"(acc[c]) : "v"(b));
+                if ((c + 1) * S / CHAINS > c * S / CHAINS)
+                    asm volatile("s_and_b64 %0, %0, %1" : "+s"(m[(u * CHAINS + c) & 3]) : "s"(keep) : "scc");
+            }
+    }
+    const uint64_t t1 = __builtin_amdgcn_s_memtime();
+    const uint64_t r1 = __builtin_amdgcn_s_memrealtime();
+    uint32_t h = (uint32_t)(m[0] ^ m[1] ^ m[2] ^ m[3]);
+#pragma unroll
+    for (int c = 0; c < CHAINS; ++c) h ^= __float_as_uint(acc[c]);
+    if (h == 0x12345678u) sink[0] = h;  // keep the chains and the masks live
+    if ((threadIdx.x & 63u) == 0) {
+        const uint32_t wv = blockIdx.x * 4 + threadIdx.x / 64;
+        out[2 * wv] = t1 - t0;
+        out[2 * wv + 1] = r1 - r0;
+    }
+}
+
+template <int S>
+void run_salu(int cus) {
+    static_assert(CHAINS == 8, "S counts scalar ANDs per 8 FMAs");
+    const int W = 8, blocks = cus * W, waves = blocks * 4;
+    uint64_t* d;
+    uint32_t* s;
+    hipMalloc(&d, waves * 2 * sizeof(uint64_t));
+    hipMalloc(&s, 4);
+    for (int rep = 0; rep < 3; ++rep) bench_salu<S><<<blocks, 256>>>(d, s);  // warm the clock
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0);
+    hipEventCreate(&e1);
+    hipEventRecord(e0);
+    bench_salu<S><<<blocks, 256>>>(d, s);
+    hipEventRecord(e1);
+    hipEventSynchronize(e1);
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    std::vector<uint64_t> h(waves * 2);
+    hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost);
+    std::vector<double> cyc, clk;
+    for (int k = 0; k < waves; ++k) {
+        cyc.push_back((double)h[2 * k]);
+        clk.push_back((double)h[2 * k] / (double)h[2 * k + 1] * 100.0);  // MHz
+    }
+    std::sort(cyc.begin(), cyc.end());
+    std::sort(clk.begin(), clk.end());
+    const double valu = (double)ITERS * UNROLL * CHAINS, salu = valu * S / CHAINS;
+    const double med_cyc = cyc[cyc.size() / 2], med_clk = clk[clk.size() / 2];
+    printf("{\"case\": \"v_fma_f32 + s_and_b64\", \"salu_per_valu\": %.2f, \"waves_per_simd\": %d, "
+           "\"valu_per_cycle_per_simd\": %.4f, \"salu_per_cycle_per_cu\": %.4f, \"clock_mhz\": %.0f, \"ms\": %.4f}\n",
+           (double)S / CHAINS, W, W * valu / med_cyc, 4.0 * W * salu / med_cyc, med_clk, ms);
+    hipFree(d);
+    hipFree(s);
+}
+
 template <class Op>
 void run(int cus) {
     for (int W : {1, 4, 8}) {
@@ -126,11 +205,19 @@ void run(int cus) {
     }
 }
 
-int main() {
+int main(int argc, char** argv) {
     hipDeviceProp_t prop;
-    hipGetDeviceProperties(&prop, 0);
+    if (hipGetDeviceProperties(&prop, 0) != hipSuccess) {
+        fprintf(stderr, "valu_cost: no GPU\n");
+        return 1;
+    }
     const int cus = prop.multiProcessorCount;
     printf("{\"device\": \"%s\", \"cus\": %d, \"clock_khz\": %d}\n", prop.gcnArchName, cus, prop.clockRate);
+    run_salu<0>(cus);
+    run_salu<2>(cus);
+    run_salu<4>(cus);
+    run_salu<8>(cus);
+    if (argc > 1 && std::string(argv[1]) == "salu") return 0;  // the scalar-mix case alone
     run<v_xor_b32>(cus);
     run<v_add_f32>(cus);
     run<v_mul_f32>(cus);
