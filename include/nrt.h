@@ -380,6 +380,70 @@ int nrt_denoise_vg_dual_device(const nrt_scene* scene, const float* dev_colour_a
                                const float* dev_albedo, const float* dev_normal, const float* dev_depth, uint32_t width,
                                uint32_t rows, const nrt_denoise_vg_opts* dopts, int32_t device, float* dev_out,
                                float* dev_out_variance, void* hip_stream);
+/* ---- adaptive sampling: a render over a list of pixels, an error estimate that selects pixels, and the loop that
+ *      refines a frame until its error is below a threshold (reference counterpart: none; the reference gives every
+ *      pixel the same samples).  Philox only, one device, whole frames. */
+/* The pixels pixels[0 .. n), linear indices y * width + x, rendered as nrt_render renders them: out_rgb[3 k ..] is,
+ * bit for bit, the pixel pixels[k] of the frame nrt_render gives for the same camera and opts (the same RNG blocks,
+ * jitter rule, pixel sums and sample window opts->sample_offset), so n * 3 floats in list order.  An index may
+ * repeat.  NRT_E_INVALID before any device is touched: opts NULL or rng = ChaCha8, a row subset (row_offset,
+ * row_stride > 1), gpus >= 1, an index >= width * height.  n = 0: NRT_OK, nothing launched.  Host buffers,
+ * synchronous. */
+int nrt_render_pixels(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                      const uint32_t* pixels, size_t n, float* out_rgb);
+/* Same over device memory on `hip_stream` (NULL = default stream), asynchronous; the indices are the caller's to
+ * keep below width * height (they are not read on the host). */
+int nrt_render_pixels_device(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                             const uint32_t* dev_pixels, size_t n, float* dev_out_rgb, void* hip_stream);
+typedef struct {
+    float threshold;      /* a pixel takes more samples until its relative error is below this; >= 0 */
+    uint32_t min_samples; /* samples every pixel gets (nrt_render_adaptive); 0 = max(4, samples_per_pixel / 8) */
+    float sigma_normal, sigma_depth; /* <= 0: the defaults 0.3, 0.5 */
+} nrt_adaptive_opts;
+/* Which pixels need more samples.  Per pixel: the means A, B of two halves of its samples over disjoint windows
+ * (3 f32 each) and n = half_samples (u32), the samples each half holds.  With a = max(albedo, 1e-3) and lum, g(p, q),
+ * the 7 x 7 window and the skipped outside taps as for nrt_denoise_vg_dual:
+ *   delta(q) = lum((A - B) / a) / 2            v(q) = n(q) delta(q)^2
+ *   Var(p)   = (sum_q w v(q) / sum_q w) / n(p),   w = exp(-g(p, q))
+ *   err(p)   = sqrt(Var(p)) / (lum(((A + B) / 2) / a) + 0.01)
+ *   select p  iff  n(p) == level  and  err(p) >= threshold
+ * v is a per-sample variance, so neighbours that hold other sample counts pool without bias; / n(p) makes it the
+ * variance of p's mean.  The comparison is not strict: threshold 0 selects every pixel of the level, also one whose
+ * halves agree exactly (err = 0: a pixel that sees only the background), so 0 renders the whole frame to the cap.
+ * pixels_out receives the selected pixels' linear indices, 32 x 8 tiles in row-major tile
+ * order and pixels row-major inside a tile (a pure function of the inputs; at most `cap` entries are written),
+ * *count their number, which may exceed cap; error_out (1 f32 per pixel, may be NULL) err(p) of every pixel.
+ * aopts->min_samples is not read.  Host buffers, device scratch for the call's duration on `device` (-1 = the
+ * current device), synchronous. */
+int nrt_adaptive_select(const float* a, const float* b, const uint32_t* half_samples, const float* albedo,
+                        const float* normal, const float* depth, uint32_t width, uint32_t rows, uint32_t level,
+                        const nrt_adaptive_opts* aopts, int32_t device, uint32_t* pixels_out, size_t cap, uint32_t* count,
+                        float* error_out);
+/* Same over device memory (dev_count: one u32 on the device), three launches enqueued on `hip_stream`, asynchronous.
+ * The scene owns the scratch (nrt_render_adaptive's: created on first use, kept, freed with the scene), under
+ * nrt_denoise_device's rules. */
+int nrt_adaptive_select_device(const nrt_scene* scene, const float* dev_a, const float* dev_b,
+                               const uint32_t* dev_half_samples, const float* dev_albedo, const float* dev_normal,
+                               const float* dev_depth, uint32_t width, uint32_t rows, uint32_t level,
+                               const nrt_adaptive_opts* aopts, int32_t device, uint32_t* dev_pixels_out, size_t cap,
+                               uint32_t* dev_count, float* dev_error_out, void* hip_stream);
+/* Render until err(p) < aopts->threshold, at most S = camera->samples_per_pixel samples per pixel.  H = S / 2,
+ * s0 = opts->sample_offset, R(s, m) = the frame of the window [s, s + m):
+ *   features: nrt_render_aov's buffers, once
+ *   level 0:  A = R(s0, n0), B = R(s0 + H, n0), n = n0 = min_samples / 2 everywhere
+ *   while n_cur < H: select at level n_cur (stop when nothing is selected); m = n_cur; the selected pixels' windows
+ *             [s0 + n_cur, + m) and [s0 + H + n_cur, + m) by two list renders A', B'; per channel
+ *             A = (n A + m A') / (n + m) in f64 rounded once to f32, the same for B; n += m; n_cur += m
+ *   out = (A + B) * 0.5f; out_samples (u32 per pixel, may be NULL) = 2 n; out_a, out_b (3 f32 per pixel, may be
+ *   NULL) = A, B, two frames nrt_denoise_vg_dual accepts
+ * A pixel not selected at its level is never selected again, so every launch has one window; a pixel that reaches
+ * S has drawn exactly the samples [s0, s0 + S) of nrt_render.  NRT_E_INVALID before any device is touched: opts NULL
+ * or ChaCha8, a row subset, gpus >= 1, aopts NULL or a threshold not >= 0, S odd, min_samples odd or < 4 (every
+ * window must jitter), S / min_samples not a power of two, sample_offset + S past nrt_render_opts.sample_offset's
+ * limits.  out_len >= width * height * 3.  The scene owns the scratch (84 B per pixel).  Synchronous. */
+int nrt_render_adaptive(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                        const nrt_adaptive_opts* aopts, float* out_rgb, size_t out_len, uint32_t* out_samples,
+                        float* out_a, float* out_b);
 /* ---- temporal accumulation in front of the variance-guided filter: SVGF (Schied et al. 2017) whole
  *      (reference counterpart: none).  The scene is static between frames, so reprojection is a
  *      function of the two cameras and the depth buffer alone. */

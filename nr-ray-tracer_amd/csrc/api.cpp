@@ -30,7 +30,9 @@ struct nrt_scene {
     MultiRender* last_multi = nullptr;
     std::vector<DenoiseScratch*> denoise;  // the filter's scratch (nrt_denoise_device), index = HIP ordinal
     std::vector<DenoiseScratch*> denoise_vg;  // the variance-guided filter's (nrt_denoise_vg_device)
+    std::vector<AdaptiveScratch*> adaptive;   // the adaptive sampler's (nrt_render_adaptive, nrt_adaptive_select_device)
     ~nrt_scene() {
+        for (AdaptiveScratch* a : adaptive) gpu_adaptive_scratch_free(a);
         for (DenoiseScratch* d : denoise) gpu_denoise_scratch_free(d);
         for (DenoiseScratch* d : denoise_vg) gpu_denoise_scratch_free(d);
         for (auto& kv : multi) gpu_multi_free(kv.second);  // (before the device scenes they render)
@@ -1087,6 +1089,220 @@ int nrt_denoise_vg_dual(const float* colour_a, const float* colour_b, const floa
                             out_variance ? st.rest() : nullptr, nullptr);
         st.download(out, st.colour(), 3);
         st.download(out_variance, st.rest(), 1);
+        return NRT_OK;
+    });
+}
+
+// ---- adaptive sampling: list renders (kernel.hpp fetch), the select chain and the refinement loop (adaptive.hip)
+namespace {
+
+// The checks the list render and the loop share, before any device is touched.
+void check_list_opts(const nrt_render_opts* o, const char* who) {
+    check_opts(o);
+    if (!o || o->rng != NRT_RNG_PHILOX)
+        throw std::invalid_argument(std::string(who) + ": rng must be Philox (a ChaCha8 stream is sequential: a pixel's "
+                                                       "samples cannot be drawn out of order)");
+    if (o->row_offset != 0 || o->row_stride > 1) throw std::invalid_argument(std::string(who) + ": whole frames only, no row subset");
+    if (o->gpus) throw std::invalid_argument(std::string(who) + ": one device, gpus must be 0");
+}
+
+// The launch parameters of the list pixels[0 .. n) (device) into out (device, n * 3 floats).
+RenderParams list_params(const nrt_scene* scene, const nrt_camera& camera, const nrt_render_opts& o, const uint32_t* pixels,
+                         uint32_t n, float* out) {
+    RenderParams p = make_params(camera, &o, (uint32_t)camera.height, scene->flat);
+    p.pixel_list = pixels;
+    p.pixel_begin = 0;
+    p.pixel_end = n;
+    p.out = out;
+    return p;
+}
+
+size_t list_length(size_t n) {
+    if (n > 0xFFFFFFFFull) throw std::invalid_argument("render_pixels: more than 2^32 - 1 list entries");
+    return n;
+}
+
+struct AdaptiveArgs {
+    float threshold, sigma_normal, sigma_depth;
+};
+AdaptiveArgs adaptive_args(const nrt_adaptive_opts* a, const char* who) {
+    if (!a) throw std::invalid_argument(std::string(who) + ": null options");
+    if (!(a->threshold >= 0.0f)) throw std::invalid_argument(std::string(who) + ": threshold must be >= 0");
+    return AdaptiveArgs{a->threshold, a->sigma_normal > 0.0f ? a->sigma_normal : 0.3f,
+                        a->sigma_depth > 0.0f ? a->sigma_depth : 0.5f};
+}
+
+void check_select(const void* a, const void* b, const void* n, const void* al, const void* nn, const void* z,
+                  uint32_t width, uint32_t rows, const void* pixels, size_t cap, const void* count) {
+    if (!a || !b || !n || !al || !nn || !z || !count || (!pixels && cap)) throw std::invalid_argument("null argument");
+    check_frame_size(width, rows, "adaptive_select");
+    if ((uint64_t)width * rows > 0xFFFFFFFFull) throw std::invalid_argument("adaptive_select: more than 2^32 - 1 pixels");
+}
+
+AdaptiveScratch* scene_adaptive(const nrt_scene* scene, int dev, size_t pixels) {
+    nrt_scene* s = const_cast<nrt_scene*>(scene);
+    std::lock_guard<std::mutex> lock(s->mu);
+    std::vector<AdaptiveScratch*>& v = s->adaptive;
+    if ((int)v.size() <= dev) v.resize((size_t)dev + 1, nullptr);
+    AdaptiveScratch* have = v[(size_t)dev];
+    v[(size_t)dev] = nullptr;  // (gpu_adaptive_scratch frees `have` before it can throw)
+    return v[(size_t)dev] = gpu_adaptive_scratch(have, pixels, dev);
+}
+
+using AdaptivePtr = std::unique_ptr<AdaptiveScratch, decltype(&gpu_adaptive_scratch_free)>;
+
+}  // namespace
+
+int nrt_render_pixels_device(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                             const uint32_t* dev_pixels, size_t n, float* dev_out_rgb, void* hip_stream) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        if (!scene || !camera || (n && (!dev_pixels || !dev_out_rgb))) throw std::invalid_argument("null argument");
+        check_list_opts(opts, "render_pixels");
+        const RenderParams p = list_params(scene, *camera, *opts, dev_pixels, (uint32_t)list_length(n), dev_out_rgb);
+        if (n == 0) return NRT_OK;
+        DeviceScene* ds = device_scene(const_cast<nrt_scene*>(scene), resolve_device(opts));
+        gpu_launch_render(ds, p, opts->precision, opts->rng, opts->trace, hip_stream);
+        return NRT_OK;
+    });
+}
+
+int nrt_render_pixels(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                      const uint32_t* pixels, size_t n, float* out_rgb) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        if (!scene || !camera || (n && (!pixels || !out_rgb))) throw std::invalid_argument("null argument");
+        check_list_opts(opts, "render_pixels");
+        RenderParams p = list_params(scene, *camera, *opts, nullptr, (uint32_t)list_length(n), nullptr);
+        const uint64_t frame = (uint64_t)p.width * p.height;
+        for (size_t k = 0; k < n; ++k)
+            if (pixels[k] >= frame)
+                throw std::invalid_argument("render_pixels: pixels[" + std::to_string(k) + "] = " + std::to_string(pixels[k]) +
+                                            " is not below width * height = " + std::to_string(frame));
+        if (n == 0) return NRT_OK;
+        const int dev = resolve_device(opts);
+        DeviceScene* ds = device_scene(const_cast<nrt_scene*>(scene), dev);
+        // the list, then the n * 3 floats
+        uint32_t* d = (uint32_t*)device_alloc(n * 4 * sizeof(uint32_t), dev);
+        try {
+            device_copy_from_host(d, pixels, n * sizeof(uint32_t), dev);
+            p.pixel_list = d;
+            p.out = (float*)(d + n);
+            p.groups_per_wave = ONE_SHOT_GROUPS_PER_WAVE;
+            gpu_launch_render(ds, p, opts->precision, opts->rng, opts->trace, nullptr);
+            device_sync(dev);
+            device_copy_to_host(out_rgb, p.out, n * 3 * sizeof(float), dev);
+        } catch (...) {
+            device_free(d, dev);
+            throw;
+        }
+        device_free(d, dev);
+        return NRT_OK;
+    });
+}
+
+int nrt_adaptive_select_device(const nrt_scene* scene, const float* dev_a, const float* dev_b,
+                               const uint32_t* dev_half_samples, const float* dev_albedo, const float* dev_normal,
+                               const float* dev_depth, uint32_t width, uint32_t rows, uint32_t level,
+                               const nrt_adaptive_opts* aopts, int32_t device, uint32_t* dev_pixels_out, size_t cap,
+                               uint32_t* dev_count, float* dev_error_out, void* hip_stream) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        if (!scene) throw std::invalid_argument("null argument");
+        check_select(dev_a, dev_b, dev_half_samples, dev_albedo, dev_normal, dev_depth, width, rows, dev_pixels_out, cap,
+                     dev_count);
+        const AdaptiveArgs a = adaptive_args(aopts, "adaptive_select");
+        const int dev = device_or_current(device);
+        AdaptiveScratch* sc = scene_adaptive(scene, dev, (size_t)width * rows);
+        gpu_adaptive_select(sc, dev_a, dev_b, dev_half_samples, dev_albedo, dev_normal, dev_depth, width, rows, level,
+                            a.threshold, a.sigma_normal, a.sigma_depth, dev_pixels_out,
+                            (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFull), dev_count, dev_error_out, hip_stream);
+        return NRT_OK;
+    });
+}
+
+int nrt_adaptive_select(const float* a, const float* b, const uint32_t* half_samples, const float* albedo,
+                        const float* normal, const float* depth, uint32_t width, uint32_t rows, uint32_t level,
+                        const nrt_adaptive_opts* aopts, int32_t device, uint32_t* pixels_out, size_t cap, uint32_t* count,
+                        float* error_out) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        check_select(a, b, half_samples, albedo, normal, depth, width, rows, pixels_out, cap, count);
+        const AdaptiveArgs g = adaptive_args(aopts, "adaptive_select");
+        const int dev = device_or_current(device);
+        const size_t px = (size_t)width * rows;
+        // the call's own scratch is its staging too: the error lands in the (unused) A' buffer
+        const AdaptivePtr sc(gpu_adaptive_scratch(nullptr, px, dev), gpu_adaptive_scratch_free);
+        const AdaptiveBuffers d = gpu_adaptive_buffers(sc.get());
+        device_copy_from_host(d.a, a, px * 3 * sizeof(float), dev);
+        device_copy_from_host(d.b, b, px * 3 * sizeof(float), dev);
+        device_copy_from_host(d.n, half_samples, px * sizeof(uint32_t), dev);
+        device_copy_from_host(d.albedo, albedo, px * 3 * sizeof(float), dev);
+        device_copy_from_host(d.normal, normal, px * 3 * sizeof(float), dev);
+        device_copy_from_host(d.depth, depth, px * sizeof(float), dev);
+        gpu_adaptive_select(sc.get(), d.a, d.b, d.n, d.albedo, d.normal, d.depth, width, rows, level, g.threshold,
+                            g.sigma_normal, g.sigma_depth, d.list, (uint32_t)px, nullptr, error_out ? d.a_new : nullptr,
+                            nullptr);
+        *count = gpu_adaptive_count(sc.get(), nullptr);
+        const size_t got = std::min<size_t>(*count, cap);
+        if (got) device_copy_to_host(pixels_out, d.list, got * sizeof(uint32_t), dev);
+        if (error_out) device_copy_to_host(error_out, d.a_new, px * sizeof(float), dev);
+        return NRT_OK;
+    });
+}
+
+int nrt_render_adaptive(const nrt_scene* scene, const nrt_camera* camera, const nrt_render_opts* opts,
+                        const nrt_adaptive_opts* aopts, float* out_rgb, size_t out_len, uint32_t* out_samples,
+                        float* out_a, float* out_b) {
+    return guarded(NRT_E_DEVICE, [&]() {
+        if (!scene || !camera || !out_rgb) throw std::invalid_argument("null argument");
+        check_list_opts(opts, "render_adaptive");
+        const AdaptiveArgs g = adaptive_args(aopts, "render_adaptive");
+        const uint64_t S = camera->samples_per_pixel;
+        if (S % 2 || S < 4) throw std::invalid_argument("render_adaptive: samples_per_pixel must be even and >= 4");
+        const uint64_t lo = aopts->min_samples ? aopts->min_samples : std::max<uint64_t>(4, S / 8);
+        if (lo % 2 || lo < 4)
+            throw std::invalid_argument("render_adaptive: min_samples must be even and >= 4 (each half window must jitter)");
+        if (lo > S || S % lo || ((S / lo) & (S / lo - 1)))
+            throw std::invalid_argument("render_adaptive: samples_per_pixel / min_samples must be a power of two (each "
+                                        "level doubles a pixel's samples)");
+        // (the whole window [s0, s0 + S) against the Philox counter's limits, the frame against the image's)
+        const RenderParams whole = make_params(*camera, opts, (uint32_t)camera->height, scene->flat);
+        const size_t px = (size_t)whole.width * whole.height;
+        if (out_len < px * 3) throw std::invalid_argument("output buffer too small");
+        check_frame_size(whole.width, whole.height, "render_adaptive");
+        const uint32_t H = (uint32_t)(S / 2), n0 = (uint32_t)(lo / 2), s0 = opts->sample_offset;
+
+        const int dev = resolve_device(opts);
+        DeviceScene* ds = device_scene(const_cast<nrt_scene*>(scene), dev);
+        AdaptiveScratch* sc = scene_adaptive(scene, dev, px);
+        const AdaptiveBuffers d = gpu_adaptive_buffers(sc);
+        gpu_launch_aov(ds, aov_params(scene, camera, opts, px), opts->trace, d.albedo, d.normal, d.depth, nullptr);
+        // the window [start, start + m): the whole frame, or the list's first `count` pixels
+        auto window = [&](uint32_t start, uint32_t m, float* out, const uint32_t* list, uint32_t count) {
+            nrt_camera c = *camera;
+            c.samples_per_pixel = m;
+            nrt_render_opts o = *opts;
+            o.sample_offset = start;
+            RenderParams p = list ? list_params(scene, c, o, list, count, out) : make_params(c, &o, (uint32_t)c.height, scene->flat);
+            p.out = out;
+            gpu_launch_render(ds, p, o.precision, o.rng, o.trace, nullptr);
+        };
+        window(s0, n0, d.a, nullptr, 0);
+        window(s0 + H, n0, d.b, nullptr, 0);
+        gpu_adaptive_fill(sc, px, n0, nullptr);
+        for (uint32_t n_cur = n0; n_cur < H; n_cur *= 2) {
+            gpu_adaptive_select(sc, d.a, d.b, d.n, d.albedo, d.normal, d.depth, whole.width, whole.height, n_cur, g.threshold,
+                                g.sigma_normal, g.sigma_depth, d.list, (uint32_t)px, nullptr, nullptr, nullptr);
+            const uint32_t count = gpu_adaptive_count(sc, nullptr);
+            if (!count) break;
+            window(s0 + n_cur, n_cur, d.a_new, d.list, count);
+            window(s0 + H + n_cur, n_cur, d.b_new, d.list, count);
+            gpu_adaptive_merge(sc, count, n_cur, nullptr);
+        }
+        // (the list and A' are free again: the frame and the sample counts)
+        gpu_adaptive_finish(sc, px, d.a_new, d.list, nullptr);
+        device_sync(dev);
+        device_copy_to_host(out_rgb, d.a_new, px * 3 * sizeof(float), dev);
+        if (out_samples) device_copy_to_host(out_samples, d.list, px * sizeof(uint32_t), dev);
+        if (out_a) device_copy_to_host(out_a, d.a, px * 3 * sizeof(float), dev);
+        if (out_b) device_copy_to_host(out_b, d.b, px * 3 * sizeof(float), dev);
         return NRT_OK;
     });
 }

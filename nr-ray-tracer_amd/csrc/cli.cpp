@@ -5,7 +5,9 @@
 // Extra flags: --precision {f64,f32}, --rng {chacha8,philox}, --gpus N, --legacy-schema (also
 // load the index schema of scenes/triangles.toml, NRT_LOAD_LEGACY_SCHEMA), --denoise[=K] (the
 // a-trous filter over the frame and its first-hit feature buffers, K = 1..5 passes, default 5),
-// --denoise-vg[=K] (the variance-guided a-trous filter instead; not with --denoise).
+// --denoise-vg[=K] (the variance-guided a-trous filter instead; not with --denoise),
+// --adaptive THRESHOLD [--min-spp N] (nrt_render_adaptive: --samples-per-pixel is the cap; f32 or f64 Philox,
+// one device; -v prints the mean samples per pixel).
 // Output formats: .png (stored deflate), .ppm, .pfm (linear f32).
 //
 // `nrt-cli convert-stl <STL> [-o FILE] [-f] [-F toml|json]` — the reference's
@@ -220,7 +222,8 @@ void usage() {
             "       [--focal-length F] [--field-of-view DEG] [--defocus-angle DEG] [--focus-distance D]\n"
             "       [--samples-per-pixel N] [--ray-max-bounces N] [-v]\n"
             "       [--precision f64|f32] [--rng chacha8|philox] [--gpus N] [--legacy-schema]\n"
-            "       [--denoise[=K] | --denoise-vg[=K] | --denoise-dual[=K]] [--sample-offset N]\n");
+            "       [--denoise[=K] | --denoise-vg[=K] | --denoise-dual[=K]] [--sample-offset N]\n"
+            "       [--adaptive THRESHOLD [--min-spp N]]\n");
     exit(2);
 }
 
@@ -237,6 +240,8 @@ int main(int argc, char** argv) {
     uint32_t denoise = 0;     // a-trous passes (0: no filter)
     uint32_t denoise_vg = 0;  // variance-guided a-trous passes (0: no filter)
     uint32_t denoise_dual = 0;  // the same passes with the variance taken between two half-sample frames
+    bool adaptive = false;    // --adaptive THRESHOLD: nrt_render_adaptive, samples_per_pixel the cap
+    nrt_adaptive_opts aopts{};
     nrt_camera_config cc{};
     nrt_render_opts opts{};
     opts.device = -1;
@@ -299,6 +304,17 @@ int main(int argc, char** argv) {
             if (v.empty() || *end || x > 0xFFFFFFFFull) die("invalid value '" + v + "' for --sample-offset");
             opts.sample_offset = (uint32_t)x;
         }
+        else if (a == "--adaptive" || a == "--min-spp") {
+            const std::string v = val();
+            char* end = nullptr;
+            if (a == "--adaptive") {
+                aopts.threshold = strtof(v.c_str(), &end);
+                adaptive = true;
+            } else {
+                aopts.min_samples = (uint32_t)strtoul(v.c_str(), &end, 10);
+            }
+            if (v.empty() || *end) die("invalid value '" + v + "' for " + a);
+        }
         else if (a.rfind("--", 0) == 0) kv.emplace_back(a, val());
         else if (scene.empty()) scene = a;
         else usage();
@@ -306,6 +322,8 @@ int main(int argc, char** argv) {
     if (scene.empty()) usage();
     if ((denoise != 0) + (denoise_vg != 0) + (denoise_dual != 0) > 1)
         die("--denoise, --denoise-vg and --denoise-dual are mutually exclusive");
+    if (adaptive && (denoise_dual || gpus > 1)) die("--adaptive renders on one device and not with --denoise-dual");
+    if (aopts.min_samples && !adaptive) die("--min-spp needs --adaptive");
     for (auto& kvp : kv) {
         const std::string& k = kvp.first;
         const std::string& v = kvp.second;
@@ -417,7 +435,17 @@ int main(int argc, char** argv) {
             die(nrt_last_error());
         }
     };
-    render_frame(img);
+    double mean_spp = (double)spp_all;
+    if (adaptive) {
+        std::vector<uint32_t> drawn((size_t)W * H);
+        if (nrt_render_adaptive(sc, &cam, &opts, &aopts, img.data(), img.size(), drawn.data(), nullptr, nullptr) != NRT_OK)
+            die(nrt_last_error());
+        double sum = 0.0;
+        for (uint32_t d : drawn) sum += (double)d;
+        mean_spp = sum / (double)drawn.size();
+    } else {
+        render_frame(img);
+    }
     if (denoise_dual) {
         if ((uint64_t)opts.sample_offset + spp_all > 0xFFFFFFFFull) die("--sample-offset + samples_per_pixel exceeds 2^32 - 1");
         opts.sample_offset += (uint32_t)cam.samples_per_pixel;
@@ -449,7 +477,8 @@ int main(int argc, char** argv) {
                     std::chrono::duration<double>(std::chrono::steady_clock::now() - td).count());
     }
     if (verbose) {
-        const double samples = (double)W * H * (double)spp_all;
+        const double samples = (double)W * H * mean_spp;
+        if (adaptive) fprintf(stderr, " Adaptive sampling: %.2f samples per pixel on average (cap %llu)\n", mean_spp, (unsigned long long)spp_all);
         fprintf(stderr, " GPU runtime start + scene upload: %.3f secs\n", init_secs);
         fprintf(stderr, " Rendering - Done in %.3f secs (%.1f Msamples/s)\n", secs, samples / secs / 1e6);
     }

@@ -94,6 +94,33 @@ void gpu_denoise_temporal(History* h, int device, const TemporalCamera& cam, con
                           float* out_variance, void* stream);
 // Waits for the device, then copies out the last frame's (m1, m2) (2 f32 per pixel) and n (1 f32); either may be null.
 void gpu_history_read(History* h, float* moments, float* length);
+// Adaptive sampling (adaptive.hip).  The scratch holds, for `pixels` pixels on `device`: the half means A, B and the
+// samples per half n, the pixel list, the list render's compact A', B', the feature buffers, and the select chain's
+// tile masks, counts and offsets (84 B per pixel and 40 B per tile); gpu_adaptive_scratch follows gpu_denoise_scratch.
+struct AdaptiveScratch;
+struct AdaptiveBuffers {
+    float *a, *b;          // 3 f32 per pixel
+    uint32_t* n;           // 1 per pixel
+    uint32_t* list;        // up to `pixels` entries
+    float *a_new, *b_new;  // 3 f32 per list entry
+    float *albedo, *normal, *depth;
+};
+AdaptiveScratch* gpu_adaptive_scratch(AdaptiveScratch* have, size_t pixels, int device);  // throws
+void gpu_adaptive_scratch_free(AdaptiveScratch* s);
+AdaptiveBuffers gpu_adaptive_buffers(const AdaptiveScratch* s);
+// Enqueue select, scan and scatter on `stream` (device pointers; the scratch's masks, counts and offsets): the pixels
+// with n == level and err >= threshold into `list` in tile order (at most `cap` entries written), their number into
+// *total (null: the scratch's own word, which gpu_adaptive_count reads), err (may be null) for every pixel.
+void gpu_adaptive_select(AdaptiveScratch* s, const float* a, const float* b, const uint32_t* n, const float* albedo,
+                         const float* normal, const float* depth, uint32_t width, uint32_t rows, uint32_t level,
+                         float threshold, float sigma_normal, float sigma_depth, uint32_t* list, uint32_t cap,
+                         uint32_t* total, float* err, void* stream);
+uint32_t gpu_adaptive_count(AdaptiveScratch* s, void* stream);  // waits for `stream`: the last select's total
+// On the scratch's own buffers: n = value everywhere; the list's first `count` entries merged with m new samples per
+// half from a_new, b_new; out = (A + B) / 2 (3 f32 per pixel) and samples = 2 n (device pointers).
+void gpu_adaptive_fill(AdaptiveScratch* s, size_t pixels, uint32_t value, void* stream);
+void gpu_adaptive_merge(AdaptiveScratch* s, uint32_t count, uint32_t m, void* stream);
+void gpu_adaptive_finish(AdaptiveScratch* s, size_t pixels, float* out, uint32_t* samples, void* stream);
 // First `count` draws of `lanes` consecutive streams starting at stream0 (tests).
 struct JitCounts {
     uint64_t compiled, launches, failed, compile_ns, disk_hits, load_retries;

@@ -1235,6 +1235,9 @@ struct ShadeSig {
     // the claim adds RenderParams::sample0: the generic kernels always, a specialised one when its launch's
     // window starts past 0 (a window at 0 compiles to the loop without the offset)
     static constexpr bool window = !cam_fixed || (CAM & SHADE_WINDOW) != 0u;
+    // fetch() may take a group's pixels from RenderParams::pixel_list: the generic kernels when the pointer is set,
+    // a specialised one when its launch is a list launch (a rectangle launch compiles to the loop without the read)
+    static constexpr bool list = !cam_fixed || (CAM & SHADE_LIST) != 0u;
 };
 using ShadeAny = ShadeSig<0xFFFFFFFFu, SHADE_CAM_RUNTIME>;
 
@@ -3678,9 +3681,22 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             const uint32_t base = p.pixel_begin + gid * P;
             double* a = acc + r * P * 3u;
             uint32_t* xy = slot_xy + r * P;
+            // a list launch (wave-uniform: the signature's bit, or the generic kernels' pointer test): the slot's
+            // pixel is the list's entry, its output slot stays base + k (flush)
+            bool listed = false;
+            if constexpr (SHADE::list) listed = SHADE::cam_fixed || p.pixel_list != nullptr;
             for (uint32_t k = lane; k < P; k += 64u) {
                 a[3 * k] = a[3 * k + 1] = a[3 * k + 2] = 0.0;
                 const uint32_t il = base + k;
+                if (listed) {
+                    uint32_t v = PAD_XY;
+                    if (il < p.pixel_end) {
+                        const uint32_t i = p.pixel_list[il];
+                        v = (i % p.width) | ((i / p.width) << 16);
+                    }
+                    xy[k] = v;
+                    continue;
+                }
                 xy[k] = il >= p.pixel_end ? PAD_XY
                                           : (il % p.width) | ((p.row_offset + (il / p.width) * p.row_stride) << 16);
             }

@@ -313,7 +313,8 @@ void gpu_launch_render(const DeviceScene* ds, const RenderParams& p, uint32_t pr
             // so a kernel never runs with facts its launch does not have.  The ChaCha8 loops read the
             // camera's mode at run time (one variant per scene)
             const uint32_t cam_sig = rng == RNG_PHILOX ? (q.defocus ? dev::SHADE_DEFOCUS : 0u) | (q.spp > 1u ? dev::SHADE_MULTI : 0u) |
-                                                             (q.sample0 ? dev::SHADE_WINDOW : 0u)
+                                                             (q.sample0 ? dev::SHADE_WINDOW : 0u) |
+                                                             (q.pixel_list ? dev::SHADE_LIST : 0u)
                                                        : dev::SHADE_CAM_RUNTIME;
             const std::string shade = ", nrt::dev::ShadeSig<" + std::to_string(ds->mat_kinds) + "u, " + std::to_string(cam_sig) + "u>";
             if (maxd == MODE_WORLD_LIST) {

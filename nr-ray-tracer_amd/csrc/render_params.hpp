@@ -25,8 +25,9 @@ namespace dev {
 constexpr int KF_PROF = 1, KF_PERLIN = 2, KF_FLAT = 4, KF_PLANES = 8, KF_TEXPAL = 16;
 // Camera-mode bits of a scene-specialised kernel's shading signature (kernel.hpp ShadeSig<MATS, CAM>):
 // a non-zero defocus disk, spp > 1, or the mode read from RenderParams at run time; SHADE_WINDOW: the launch's
-// sample window starts past 0 (RenderParams::sample0: without the bit the kernel never reads it).
-constexpr uint32_t SHADE_DEFOCUS = 1u, SHADE_MULTI = 2u, SHADE_CAM_RUNTIME = 4u, SHADE_WINDOW = 8u;
+// sample window starts past 0 (RenderParams::sample0: without the bit the kernel never reads it); SHADE_LIST: the
+// launch's pixels come from a list (RenderParams::pixel_list, read under the same rule).
+constexpr uint32_t SHADE_DEFOCUS = 1u, SHADE_MULTI = 2u, SHADE_CAM_RUNTIME = 4u, SHADE_WINDOW = 8u, SHADE_LIST = 16u;
 // Exact kernel, small scenes: at most this many slots of the culling tree are tested in slot order
 // instead of walked (EXACT_SIG_SLOTS / EXACT_SIG_SLOTS_PF; host default and launcher share it)
 constexpr uint32_t EXACT_SLOTS_MAX = 32;
@@ -106,6 +107,11 @@ struct RenderParams {
     // launch's spp draws the blocks of sample index sample0 + cur (kernel.hpp, where a lane claims its sample;
     // a scene-specialised kernel reads it only when its signature has SHADE_WINDOW)
     uint32_t sample0;
+    // Philox, list launch (nrt_render_pixels): slot pixel_begin + k of the launch renders the pixel of linear index
+    // pixel_list[pixel_begin + k] = y * width + x (device, pixel_end entries; all rows: row_offset 0, row_stride 1)
+    // and writes it to out + 3 (pixel_begin + k): a compact (n, 3) array in list order.  nullptr: the launch's
+    // pixels are the rectangle's (kernel.hpp fetch; a scene-specialised kernel reads it only with SHADE_LIST)
+    const uint32_t* pixel_list;
 };
 
 }  // namespace nrt

@@ -88,6 +88,11 @@ class _DenoiseTemporalOpts(C.Structure):
                 ("sigma_depth", C.c_float), ("alpha_min", C.c_float), ("tau_z", C.c_float), ("tau_n", C.c_float)]
 
 
+class _AdaptiveOpts(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("min_samples", C.c_uint32), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint64)
 
 # Every symbol include/nrt.h declares, with its ctypes signature.
@@ -153,6 +158,19 @@ SIGNATURES = {
                                       C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nrt_denoise_vg_dual_device": (C.c_int, [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(_DenoiseVgOpts),
                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrt_render_pixels": (C.c_int, [C.c_void_p, C.POINTER(_Camera), C.POINTER(_RenderOpts), C.POINTER(C.c_uint32),
+                                    C.c_size_t, C.POINTER(C.c_float)]),
+    "nrt_render_pixels_device": (C.c_int, [C.c_void_p, C.POINTER(_Camera), C.POINTER(_RenderOpts), C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p]),
+    "nrt_adaptive_select": (C.c_int, [C.POINTER(C.c_float)] * 2 + [C.POINTER(C.c_uint32)] + [C.POINTER(C.c_float)] * 3 +
+                            [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_AdaptiveOpts), C.c_int32,
+                             C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "nrt_adaptive_select_device": (C.c_int, [C.c_void_p] * 7 + [C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.POINTER(_AdaptiveOpts), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "nrt_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(_Camera), C.POINTER(_RenderOpts), C.POINTER(_AdaptiveOpts),
+                                      C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float)]),
     "nrt_history_new": (C.c_void_p, [C.c_uint32, C.c_uint32, C.c_int32]),
     "nrt_history_free": (None, [C.c_void_p]),
     "nrt_history_reset": (C.c_int, [C.c_void_p]),
@@ -499,6 +517,73 @@ class Scene:
                                 out.ctypes.data_as(C.POINTER(C.c_float)), out.size, cb, None))
         return out
 
+    def render_pixels(self, pixels, camera: Optional[Camera] = None, precision: str = "f32", device: int = -1,
+                      trace: str = "auto", sample_offset: int = 0, rng: str = "philox", row_offset: int = 0,
+                      row_stride: int = 1, gpus: int = 0) -> np.ndarray:
+        """The pixels of linear indices y * W + x in `pixels`, as (n, 3) float32 in list order (nrt_render_pixels):
+        row k is, bit for bit, pixel pixels[k] of render(...) with the same camera, precision, trace and
+        sample_offset.  Philox, whole frames, one device: another rng, a row subset or gpus >= 1 is an invalid
+        argument, as is an index >= W * H."""
+        cam = camera or self.camera
+        if cam is None:
+            raise ValueError("no camera")
+        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset)
+        px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        out = np.empty((px.size, 3), dtype=np.float32)
+        _check(lib().nrt_render_pixels(self._h, C.byref(cam._c()), C.byref(o), px.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       px.size, out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
+    def render_pixels_device(self, pixels_ptr: int, n: int, out_ptr: int, camera: Optional[Camera] = None,
+                             precision: str = "f32", device: int = -1, trace: str = "auto", sample_offset: int = 0,
+                             stream: int = 0) -> None:
+        """Enqueue a list render over device memory (nrt_render_pixels_device): n uint32 indices, n * 3 floats."""
+        cam = camera or self.camera
+        o = _opts(precision, "philox", device, 0, 1, trace, 0, sample_offset)
+        _check(lib().nrt_render_pixels_device(self._h, C.byref(cam._c()), C.byref(o), C.c_void_p(pixels_ptr), n,
+                                              C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+    def render_adaptive(self, camera: Optional[Camera] = None, threshold: float = 0.05, min_samples: int = 0,
+                        precision: str = "f32", device: int = -1, trace: str = "auto", sample_offset: int = 0,
+                        samples_out: Optional[np.ndarray] = None, halves_out=None, rng: str = "philox",
+                        row_offset: int = 0, row_stride: int = 1, gpus: int = 0, sigma_normal: float = 0.3,
+                        sigma_depth: float = 0.5) -> np.ndarray:
+        """Adaptive sampling (nrt_render_adaptive): every pixel gets min_samples samples (0: max(4, spp / 8)), then
+        the pixels whose estimated relative error is not below `threshold` double theirs, level by level, up to the
+        camera's samples_per_pixel.  Returns the (H, W, 3) float32 frame.  samples_out: an (H, W) uint32 array for
+        the samples each pixel drew.  halves_out: a pair of (H, W, 3) float32 arrays for the two half-sample frames
+        A, B (the frame is their mean; nrt.denoise_vg_dual accepts them)."""
+        cam = camera or self.camera
+        if cam is None:
+            raise ValueError("no camera")
+        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset)
+        a = _AdaptiveOpts(threshold, min_samples, sigma_normal, sigma_depth)
+        out = np.empty((cam.height, cam.width, 3), dtype=np.float32)
+        if samples_out is not None and (samples_out.dtype != np.uint32 or not samples_out.flags.c_contiguous or
+                                        samples_out.shape != out.shape[:2]):
+            raise NrtError(-1, "render_adaptive: samples_out must be a contiguous uint32 array of shape (H, W)")
+        halves = tuple(halves_out) if halves_out is not None else (None, None)
+        if len(halves) != 2 or any(h is not None and (h.dtype != np.float32 or not h.flags.c_contiguous or
+                                                      h.shape != out.shape) for h in halves):
+            raise NrtError(-1, "render_adaptive: halves_out must be two contiguous float32 arrays of shape (H, W, 3)")
+        fp = lambda x: x.ctypes.data_as(C.POINTER(C.c_float)) if x is not None else None  # noqa: E731
+        _check(lib().nrt_render_adaptive(self._h, C.byref(cam._c()), C.byref(o), C.byref(a), fp(out), out.size,
+                                         samples_out.ctypes.data_as(C.POINTER(C.c_uint32)) if samples_out is not None
+                                         else None, fp(halves[0]), fp(halves[1])))
+        return out
+
+    def adaptive_select_device(self, a_ptr: int, b_ptr: int, half_samples_ptr: int, albedo_ptr: int, normal_ptr: int,
+                               depth_ptr: int, width: int, rows: int, level: int, threshold: float, pixels_ptr: int,
+                               cap: int, count_ptr: int, error_ptr: int = 0, sigma_normal: float = 0.3,
+                               sigma_depth: float = 0.5, device: int = -1, stream: int = 0) -> None:
+        """Enqueue the selection over device memory (nrt_adaptive_select_device; the scene owns the scratch);
+        count_ptr: one uint32 on the device, error_ptr may be 0."""
+        a = _AdaptiveOpts(threshold, 0, sigma_normal, sigma_depth)
+        _check(lib().nrt_adaptive_select_device(self._h, *(C.c_void_p(x) for x in (a_ptr, b_ptr, half_samples_ptr,
+                                                albedo_ptr, normal_ptr, depth_ptr)), width, rows, level, C.byref(a),
+                                                device, C.c_void_p(pixels_ptr), cap, C.c_void_p(count_ptr),
+                                                C.c_void_p(error_ptr), C.c_void_p(stream)))
+
     def render_aov(self, camera: Optional[Camera] = None, trace: str = "auto", device: int = -1,
                    row_offset: int = 0, row_stride: int = 1, gpus: int = 0) -> dict:
         """First-hit feature buffers (nrt_render_aov): {"albedo": (rows, W, 3), "normal": (rows, W, 3),
@@ -781,6 +866,28 @@ def denoise_vg_dual(frame_a: np.ndarray, frame_b: np.ndarray, albedo: np.ndarray
     _check(lib().nrt_denoise_vg_dual(p[0], b.ctypes.data_as(C.POINTER(C.c_float)), *p[1:4], c.shape[1], c.shape[0],
                                      C.byref(d), device, p[4], p[5]))
     return out
+
+
+def adaptive_select(a: np.ndarray, b: np.ndarray, half_samples: np.ndarray, albedo: np.ndarray, normal: np.ndarray,
+                    depth: np.ndarray, level: int, threshold: float, sigma_normal: float = 0.3, sigma_depth: float = 0.5,
+                    device: int = -1):
+    """Which pixels need more samples (nrt_adaptive_select): a, b the (rows, W, 3) means of two halves of each pixel's
+    samples, half_samples the (rows, W) samples per half; returns (pixels, error): the uint32 linear indices of the
+    pixels with half_samples == level whose estimated relative error is not below threshold, in the order a list render
+    takes them (32 x 8 tiles row-major, pixels row-major inside a tile), and the (rows, W) float32 error."""
+    (c, _, _, _, _, _), p = _frame_args("adaptive_select", "a", a, albedo, normal, depth, None, None)
+    bb = np.ascontiguousarray(b, dtype=np.float32)
+    n = np.ascontiguousarray(half_samples, dtype=np.uint32)
+    if bb.shape != c.shape or n.shape != c.shape[:2]:
+        raise NrtError(-1, f"adaptive_select: b {bb.shape} / half_samples {n.shape} do not match a {c.shape}")
+    pixels, err = np.empty(n.size, np.uint32), np.empty(n.shape, np.float32)
+    count = C.c_uint32(0)
+    o = _AdaptiveOpts(threshold, 0, sigma_normal, sigma_depth)
+    _check(lib().nrt_adaptive_select(p[0], bb.ctypes.data_as(C.POINTER(C.c_float)), n.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                     *p[1:4], c.shape[1], c.shape[0], level, C.byref(o), device,
+                                     pixels.ctypes.data_as(C.POINTER(C.c_uint32)), pixels.size, C.byref(count),
+                                     err.ctypes.data_as(C.POINTER(C.c_float))))
+    return pixels[:count.value].copy(), err
 
 
 class History:
