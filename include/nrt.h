@@ -137,6 +137,25 @@ typedef struct {
      * a non-zero offset (the reference stream is sequential: where a window starts depends on the lengths
      * of the paths before it).  Row selection and gpus = N take it unchanged; nrt_render_aov* ignores it. */
     uint32_t sample_offset;
+    /* Next-event estimation, f32 + Philox in the world-list and world-BVH modes (reference counterpart: none; the
+     * expected frame is the reference's).  Non-zero: at every Lambertian hit of the ray with bounce index b, when
+     * b + 1 < ray_max_bounces, one light is picked (probability P: area x the largest component of Le = intensity
+     * x colour), one point y on it (quads and triangles uniform in area, a sphere uniform in the cone it subtends),
+     * and one shadow ray x -> y adds  throughput x albedo x p_ref(n.w) x Le x W  when its closest hit is the light
+     * itself.  p_ref is the density of the reference's scatter direction n + p / |p|^2 (not a cosine lobe: an eighth
+     * of it lies below the surface), W = |n_l.w| area / (r^2 P) for a quad or triangle (two-sided) and
+     * 2 pi (1 - cos theta_max) / P for a sphere.  The ray scattered from that hit then adds nothing when it ends
+     * on a light by chance; camera rays and rays leaving a Metal or Dielectric count lights as before.  The
+     * scatter draws keep their blocks; the light draws take Philox2x32 blocks of their own, step 127 + (b + 1).
+     * Limit: a hit on or inside an emissive sphere gets no light from that sphere.
+     * 0: every frame as without the field, bit for bit; a scene without lights renders the plain frame too.
+     * Before any device is touched: NRT_E_INVALID for ChaCha8 (the reference stream has no such draws) and for
+     * ray_max_bounces > 126; NRT_E_UNSUPPORTED for f64, the instance-BVH mode, gpus >= 1, and a scene with a
+     * light that cannot be sampled (an emissive material whose texture is not a solid colour, a moving emissive
+     * sphere, an emissive sphere the f32 kernels test in f64, more than 4096 lights: nrt_scene_stats.lights).
+     * Row selection, sample_offset, nrt_render_pixels and nrt_render_adaptive take it unchanged; nrt_render_aov*
+     * ignores it. */
+    uint32_t direct_light;
 } nrt_render_opts;
 
 typedef struct {
@@ -156,6 +175,7 @@ typedef struct {
      * band; else RGB8T, 3 B per texel in 128-B tiles of 8 x 5; RGBA8 tiles; RGB32F for constructor
      * images with values other than k/255) plus the Perlin permutation tables of Noise / Marble */
     uint64_t texel_bytes;
+    uint32_t lights; /* primitives whose material is a DiffuseLight (instances flattened: one per placement) */
 } nrt_scene_stats;
 /* Exact-kernel traversal (same closest hit and tie-break as BVH::hit, object.rs:89-121):
  *   BVH      the reference tree, box by box

@@ -315,6 +315,25 @@ RenderParams make_params(const nrt_camera& c, const nrt_render_opts* o, uint32_t
         throw std::invalid_argument("sample_offset needs rng = Philox: a ChaCha8 stream is sequential, so a window's "
                                     "start depends on the paths before it");
     }
+    if (o && o->direct_light) {  // (every check before a device is touched)
+        if (o->rng != NRT_RNG_PHILOX)
+            throw std::invalid_argument("direct_light needs rng = Philox: the reference's ChaCha8 stream has no light draws");
+        if (p.max_bounces > PHILOX2_DIRECT_MAX_BOUNCES)
+            throw std::invalid_argument("direct_light: ray_max_bounces <= 126 (the light draws take the Philox2x32 steps "
+                                        "127 + bounce)");
+        if (o->precision != NRT_PRECISION_F32) throw UnsupportedError("direct_light: the f32 kernels only");
+        if (o->gpus) throw UnsupportedError("direct_light: one device only (gpus = 0)");
+        // the mode gpu_fast_maxd will pick for this scene
+        const bool list = f.world_ok && f.list_ok && !f.wprims.empty(), bvh = f.wbvh_ok && f.wbvh_f32_ok;
+        const bool world = o->trace == NRT_TRACE_WORLD_LIST ? list
+                           : o->trace == NRT_TRACE_WORLD_BVH ? bvh
+                           : o->trace == NRT_TRACE_AUTO     ? ((list && f.world_units <= NRT_WORLD_LIST_MAX) || bvh)
+                                                            : false;
+        if (!world && (o->trace == NRT_TRACE_BVH || o->trace == NRT_TRACE_AUTO))
+            throw UnsupportedError("direct_light: the world-list and world-BVH modes only (not the instance BVH)");
+        if (!f.lights_why.empty()) throw UnsupportedError("direct_light: the scene has " + f.lights_why);
+        p.direct_light = f.lights.empty() ? 0u : 1u;  // no lights: the plain frame
+    }
     // Radiance grid 2^-k: a sample's radiance is at most max(background, emission) x
     // albedo^bounces; k keeps spp such values below 2^52, so the pixel sums are exact
     // (order-free).  Albedo > 1 is counted over at most 8 bounces: past that the sums
@@ -338,7 +357,9 @@ RenderParams make_params(const nrt_camera& c, const nrt_render_opts* o, uint32_t
         alb = texmax;
         double lg = std::log2(std::fmax(emit, 1e-300)) + std::log2((double)p.spp) +
                     std::log2(alb) * (double)std::min<uint32_t>(p.max_bounces, 8u);
-        int k = 50 - (int)std::ceil(std::fmax(lg, -100.0));
+        // (direct_light: a light sample's weight |n_l.w| area / (r^2 P) has no bound near a light; the sums' expectation
+        // is the plain frame's, and four more bits of headroom keep them exact for weights of 16 x emission x spp)
+        int k = (p.direct_light ? 46 : 50) - (int)std::ceil(std::fmax(lg, -100.0));
         k = std::max(-900, std::min(k, 900));
         // f32 kernels scale and round in f32 (exact for a power of two in f32 range): the grid
         // exponent stays in [-126, 127] (only radiance x spp beyond 2^176 or below 2^-77 moves it)
@@ -798,6 +819,7 @@ RenderParams aov_params(const nrt_scene* scene, const nrt_camera* camera, const 
     o.precision = NRT_PRECISION_F32;  // (the camera's f32 copy; no sample pool is sized)
     o.rng = NRT_RNG_CHACHA8;
     o.sample_offset = 0;  // (one un-jittered ray per pixel: no window)
+    o.direct_light = 0;   // (first hits only)
     RenderParams p = make_params(*camera, &o, rows, scene->flat);
     if (n_pixels < (size_t)rows * p.width) throw std::invalid_argument("feature buffers too small");
     return p;
@@ -1377,6 +1399,7 @@ int nrt_scene_stats_get(const nrt_scene* scene, nrt_scene_stats* out) {
         for (const DTexture& t : f.textures)
             if (t.kind == TEX_IMAGE) out->texel_formats |= 1u << t.format;
         out->texel_bytes = (uint64_t)f.texels.size() * sizeof(uint32_t);
+        out->lights = f.n_lights;
         return NRT_OK;
     });
 }

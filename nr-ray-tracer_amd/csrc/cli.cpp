@@ -223,7 +223,7 @@ void usage() {
             "       [--samples-per-pixel N] [--ray-max-bounces N] [-v]\n"
             "       [--precision f64|f32] [--rng chacha8|philox] [--gpus N] [--legacy-schema]\n"
             "       [--denoise[=K] | --denoise-vg[=K] | --denoise-dual[=K]] [--sample-offset N]\n"
-            "       [--adaptive THRESHOLD [--min-spp N]]\n");
+            "       [--adaptive THRESHOLD [--min-spp N]] [--direct-light]\n");
     exit(2);
 }
 
@@ -304,6 +304,7 @@ int main(int argc, char** argv) {
             if (v.empty() || *end || x > 0xFFFFFFFFull) die("invalid value '" + v + "' for --sample-offset");
             opts.sample_offset = (uint32_t)x;
         }
+        else if (a == "--direct-light") opts.direct_light = 1;  // (f32 + Philox, one device: nrt_render_opts)
         else if (a == "--adaptive" || a == "--min-spp") {
             const std::string v = val();
             char* end = nullptr;

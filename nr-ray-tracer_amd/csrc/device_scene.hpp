@@ -344,6 +344,29 @@ struct alignas(16) DTexture {
     double scale;      // checker scale; noise/marble: Fbm scale factor
 };
 
+// A light the f32 Philox kernels sample on purpose (nrt_render_opts.direct_light; flatten.cpp build_lights): a world
+// primitive whose material is a DiffuseLight with a solid colour.  80 bytes, five 16-byte loads per sample.
+//   quad / triangle  p, u, v in world space; n = the unit normal; w = area / P (area |u x v|, a triangle's half)
+//   sphere           p = the centre, u[0] = the radius; w = 2 pi / P
+// P = the light's pick probability (area x the largest component of Le, normalised), cdf = the sum of P up to and
+// including this light on the 2^-LIGHT_PICK_BITS grid of the pick draw (P is the grid's own difference, so the
+// pick is exact); Le = intensity x colour; prim_list / prim_bvh = the light's own record in the world list
+// (after box and room fusion) and in the world BVH's primitive order: a shadow ray sees the light iff its
+// closest hit is that record.
+struct alignas(16) DLight {
+    float p[3], cdf;
+    float u[3], w;
+    float v[3];
+    uint32_t kind;  // PRIM_QUAD / PRIM_TRIANGLE / PRIM_SPHERE
+    float n[3];
+    uint32_t prim_list;
+    float Le[3];
+    uint32_t prim_bvh;
+};
+static_assert(sizeof(DLight) == 80, "five 16-byte loads per light record");
+constexpr uint32_t LIGHT_MAX = 4096, LIGHT_PICK_BITS = 18;
+constexpr uint32_t LIGHT_SCAN_MAX = 8;  // up to this many lights the pick scans the table through the scalar cache
+
 // What the kernel gets: device pointers + sizes (per precision).
 template <typename Real>
 struct DSceneView {
@@ -384,6 +407,8 @@ struct DSceneView {
     // f64 view: 4-wide nodes of that tree when the tree, wxprims and wexact are small enough to be
     // staged in LDS with the scene (XSTAGE_MAX_BYTES; the Cornell box: 2 KB), else 0
     uint32_t n_xstage;
+    const DLight* lights;  // f32 view: the light table (direct_light kernels only), n_lights records
+    uint32_t n_lights;
 };
 constexpr uint32_t XSTAGE_MAX_BYTES = 8192;
 

@@ -549,8 +549,9 @@ struct Flattener {
 
     // Axis quads that each cover a whole face of the bounding box of all axis
     // quads (e.g. the Cornell room's walls) -> one PRIM_ABOX unit (device_scene.hpp).
+    // (from: the wprims index of every entry of every unit, SIZE_MAX for headers and empty slots: build_lights)
     void fuse_room(std::vector<std::vector<DPrimWorld<double>>>& units, std::vector<uint32_t>& kind,
-                   std::vector<size_t>& src) {
+                   std::vector<size_t>& src, std::vector<std::vector<size_t>>& from) {
         std::vector<size_t> aq;
         for (size_t u = 0; u < units.size(); ++u)
             if (kind[u] >= PRIM_QUAD_X && kind[u] <= PRIM_QUAD_Z) aq.push_back(u);
@@ -599,6 +600,7 @@ struct Flattener {
                 if (face[a][sd] >= 0) cls |= units[face[a][sd]][0].meta >> WCLASS_SHIFT;
         if (cls == (WCLASS_WIN | WCLASS_LOSE)) return;
         std::vector<DPrimWorld<double>> unit(1 + 6);
+        std::vector<size_t> unit_from(1 + 6, SIZE_MAX);
         DPrimWorld<double>& h = unit[0];
         h = DPrimWorld<double>{};
         for (int r = 0; r < 3; ++r) { h.N[r] = lo[r]; h.AB[r] = hi[r]; }
@@ -610,6 +612,7 @@ struct Flattener {
                 if (face[a][sd] >= 0) {
                     if (src[face[a][sd]] != SIZE_MAX) tie_form[src[face[a][sd]]] = axis_form(a, sd ? hi[a] : lo[a]);
                     unit[1 + slot] = units[face[a][sd]][0];
+                    unit_from[1 + slot] = from[face[a][sd]][0];
                     map |= (uint32_t)slot << (3 * slot);
                     present |= 1u << slot;
                     dead[face[a][sd]] = true;
@@ -622,14 +625,17 @@ struct Flattener {
         std::vector<std::vector<DPrimWorld<double>>> nu;
         std::vector<uint32_t> nk;
         std::vector<size_t> ns;
+        std::vector<std::vector<size_t>> nf;
         for (size_t u = 0; u < units.size(); ++u)
-            if (!dead[u]) { nu.push_back(std::move(units[u])); nk.push_back(kind[u]); ns.push_back(src[u]); }
+            if (!dead[u]) { nu.push_back(std::move(units[u])); nk.push_back(kind[u]); ns.push_back(src[u]); nf.push_back(std::move(from[u])); }
         nu.push_back(std::move(unit));
         nk.push_back(PRIM_ABOX);
         ns.push_back(SIZE_MAX);
+        nf.push_back(std::move(unit_from));
         units.swap(nu);
         kind.swap(nk);
         src.swap(ns);
+        from.swap(nf);
     }
 
     // Six consecutive quads closing a parallelepiped -> PRIM_BOX header (device_scene.hpp).
@@ -1047,6 +1053,79 @@ struct Flattener {
         out.wbvh_f32_ok = !far_sphere;
     }
 
+    // The light table (device_scene.hpp DLight) from the world primitives in depth-first order (`walked`, with
+    // wgeom's world p, u, v) whose material is a DiffuseLight.  Pick probabilities: area x the largest component
+    // of Le, cumulated on the pick draw's 2^-LIGHT_PICK_BITS grid with every light at least one grid point wide,
+    // so the probability a record states is the one the kernel's compare realises.
+    void build_lights(const std::vector<DPrimWorld<double>>& walked, const std::vector<uint32_t>& list_index) {
+        std::vector<uint32_t> bvh_index(walked.size(), 0xFFFFFFFFu);
+        for (size_t k = 0; k < out.wbvh.order.size(); ++k)
+            if (out.wbvh.order[k] < bvh_index.size()) bvh_index[out.wbvh.order[k]] = (uint32_t)k;
+        std::vector<DLight> lights;
+        std::vector<double> weight;
+        const double pi = 3.14159265358979323846;
+        for (size_t i = 0; i < walked.size(); ++i) {
+            const DPrimWorld<double>& w = walked[i];
+            const DMaterial& m = out.materials[(w.meta >> WKIND_BITS) & WMAT_MASK];
+            if (m.kind != MAT_DIFFUSE_LIGHT) continue;
+            ++out.n_lights;
+            const DTexture& t = out.textures[m.texture];
+            const uint32_t kind = w.meta & WKIND_MASK;
+            if (t.kind != TEX_SOLID) out.lights_why = "an emissive material whose texture is not a solid colour";
+            DLight l{};
+            double area = 0.0;
+            if (kind == PRIM_SPHERE) {
+                if (w.AB[0] != 0.0 || w.AB[1] != 0.0 || w.AB[2] != 0.0) out.lights_why = "a moving emissive sphere";
+                else if (w.AB[6] != 0.0) out.lights_why = "an emissive sphere the f32 kernels test in f64";
+                const double r = std::fabs(w.D);
+                for (int k = 0; k < 3; ++k) l.p[k] = (float)w.N[k];
+                l.u[0] = (float)r;
+                area = 4.0 * pi * r * r;
+                l.w = (float)(2.0 * pi);
+            } else {
+                const auto& g = wgeom[i];
+                const V3a c = {g[1][1] * g[2][2] - g[1][2] * g[2][1], g[1][2] * g[2][0] - g[1][0] * g[2][2],
+                               g[1][0] * g[2][1] - g[1][1] * g[2][0]};
+                const double cl = std::sqrt(vdot(c, c));
+                area = kind == PRIM_TRIANGLE ? 0.5 * cl : cl;
+                for (int k = 0; k < 3; ++k) {
+                    l.p[k] = (float)g[0][k];
+                    l.u[k] = (float)g[1][k];
+                    l.v[k] = (float)g[2][k];
+                    l.n[k] = (float)(cl > 0.0 ? c[k] / cl : 0.0);
+                }
+                l.w = (float)area;
+            }
+            l.kind = kind;
+            double le = 0.0;
+            for (int k = 0; k < 3; ++k) {
+                l.Le[k] = (float)(m.param * t.color[k]);
+                le = std::fmax(le, std::fabs(m.param * t.color[k]));
+            }
+            l.prim_list = list_index[i];
+            l.prim_bvh = bvh_index[i];
+            lights.push_back(l);
+            weight.push_back(std::isfinite(area * le) && area * le > 0.0 ? area * le : 1e-300);
+        }
+        if (out.n_lights > LIGHT_MAX) out.lights_why = "more than 4096 lights";
+        if (!out.lights_why.empty()) return;
+        double total = 0.0, cum = 0.0;
+        for (double x : weight) total += x;
+        const uint32_t grid = 1u << LIGHT_PICK_BITS;
+        uint32_t q = 0;
+        for (size_t i = 0; i < lights.size(); ++i) {
+            cum += weight[i];
+            const uint32_t rest = (uint32_t)(lights.size() - 1 - i);  // lights after this one: a grid point each
+            uint32_t qi = (uint32_t)std::llround(cum / total * (double)grid);
+            qi = std::min(std::max(qi, q + 1u), grid - rest);
+            if (rest == 0) qi = grid;
+            lights[i].cdf = (float)qi / (float)grid;
+            lights[i].w *= (float)grid / (float)(qi - q);  // / P
+            q = qi;
+        }
+        out.lights = std::move(lights);
+    }
+
     // DXform of a transform node (every chain was emitted by instance()).
     std::map<const Object*, uint32_t> xform_of;
     uint32_t xform_index(const Object* t) {
@@ -1132,6 +1211,8 @@ struct Flattener {
         std::vector<std::vector<DPrimWorld<double>>> units;
         std::vector<uint32_t> unit_kind;
         std::vector<size_t> unit_src;  // wprims index of a single-primitive unit
+        std::vector<std::vector<size_t>> unit_from;  // wprims index of every entry (SIZE_MAX: a header)
+        const std::vector<DPrimWorld<double>> walked = out.wprims;  // depth-first order (build_lights)
         for (size_t i = 0; i < out.wprims.size();) {
             DPrimWorld<double> hdr;
             if (i + 6 <= out.wprims.size() && fuse_box(i, hdr)) {
@@ -1140,6 +1221,7 @@ struct Flattener {
                 units.push_back(std::move(u));
                 unit_kind.push_back(box_y ? PRIM_BOXY : PRIM_BOX);
                 unit_src.push_back(SIZE_MAX);
+                unit_from.push_back({SIZE_MAX, i, i + 1, i + 2, i + 3, i + 4, i + 5});
                 i += 6;
             } else {
                 DPrimWorld<double> w = out.wprims[i];
@@ -1154,10 +1236,11 @@ struct Flattener {
                 units.push_back({w});
                 unit_kind.push_back(w.meta & WKIND_MASK);
                 unit_src.push_back(i);
+                unit_from.push_back({i});
                 ++i;
             }
         }
-        fuse_room(units, unit_kind, unit_src);
+        fuse_room(units, unit_kind, unit_src, unit_from);
         // the world list resolves a coplanar tie by order alone: only when both faces compute
         // bit-identical t (equal tie forms); otherwise the scene uses the world BVH's keys
         for (const auto& [lo, hi] : tie_pairs) {
@@ -1188,10 +1271,14 @@ struct Flattener {
         });
         std::vector<DPrimWorld<double>> fused;
         std::vector<uint32_t> kinds;
+        std::vector<uint32_t> list_index(walked.size(), 0xFFFFFFFFu);  // world-list record of each walked primitive
         for (size_t k : order) {
+            for (size_t e = 0; e < units[k].size(); ++e)
+                if (unit_from[k][e] != SIZE_MAX) list_index[unit_from[k][e]] = (uint32_t)(fused.size() + e);
             fused.insert(fused.end(), units[k].begin(), units[k].end());
             kinds.push_back(unit_kind[k]);
         }
+        build_lights(walked, list_index);
         out.wprims.swap(fused);
         out.world_units = kinds.size();
         const uint32_t one = 1u << WRUN_KIND_BITS;
@@ -1286,6 +1373,11 @@ constexpr float EXACT_SAH_PRIM_COST = 3.0f;
 FlatScene flatten_scene(const ObjectPtr& top) {
     Flattener f;
     f.run(top.get());
+    if (!f.out.world_ok) {  // no world primitives: the emissive primitives of the exact tree, none of them sampled
+        for (const DPrim<double>& pr : f.out.prims)
+            f.out.n_lights += f.out.materials[pr.material].kind == MAT_DIFFUSE_LIGHT ? 1u : 0u;
+        if (f.out.n_lights) f.out.lights_why = "a scene that does not flatten to world space";
+    }
     map_exact_refs(f.out);
     if (!f.out.wexact.empty()) {
         // several instance chains (or the top level and a chain): a tree of its own for the

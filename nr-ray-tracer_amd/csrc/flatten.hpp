@@ -51,6 +51,13 @@ struct FlatScene {
     std::vector<DExactRef> wexact;
     std::vector<DPrimWorld<double>> wexact_prims;  // world primitive of each exact-tree slot (prefilter)
     std::vector<uint32_t> wprims_kind;  // kind of each world primitive (depth-first rank)
+    // Light table of the direct_light kernels (device_scene.hpp DLight): one record per world primitive whose
+    // material is a DiffuseLight, in the reference's depth-first order.  n_lights counts them (scenes that do not
+    // flatten: the emissive primitives of the exact tree); lights_why is non-empty when one of them cannot be
+    // sampled (a textured emission, a moving sphere, a sphere tested in f64, too many), and `lights` is then empty.
+    std::vector<DLight> lights;
+    uint32_t n_lights = 0;
+    std::string lights_why;
     const WorldBvh& exact_tree() const { return wbvh_x.order.empty() ? wbvh : wbvh_x; }
 };
 

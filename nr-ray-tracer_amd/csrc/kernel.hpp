@@ -1238,6 +1238,8 @@ struct ShadeSig {
     // fetch() may take a group's pixels from RenderParams::pixel_list: the generic kernels when the pointer is set,
     // a specialised one when its launch is a list launch (a rectangle launch compiles to the loop without the read)
     static constexpr bool list = !cam_fixed || (CAM & SHADE_LIST) != 0u;
+    // a direct_light launch of a specialised kernel (the generic kernels: KF_DIRECT)
+    static constexpr bool direct = cam_fixed && (CAM & SHADE_DIRECT) != 0u;
 };
 using ShadeAny = ShadeSig<0xFFFFFFFFu, SHADE_CAM_RUNTIME>;
 
@@ -1251,8 +1253,10 @@ __device__ __forceinline__ void sig_runs(WorldSig<RUNS...>, ConstPrimWorld<float
      ...);
 }
 
+// t_max: hits beyond it do not count (a shadow ray's query ends just past its light)
 template <typename R, int MAXD, bool FLAT = false, class SIG = NoSig>
-__device__ __forceinline__ bool trace_world(const DSceneView<R>& sc, const Ray<R>& ray, HitMin<R, MAXD>& hm) {
+__device__ __forceinline__ bool trace_world(const DSceneView<R>& sc, const Ray<R>& ray, HitMin<R, MAXD>& hm,
+                                            float t_max = INFINITY) {
     static_assert(sizeof(R) == 4, "world-space mode is an f32-kernel mode");
 #if NRT_WL_RELOAD
     // the records' scalar loads stay inside the loop (the base laundered per query): loop-invariant
@@ -1264,7 +1268,7 @@ __device__ __forceinline__ bool trace_world(const DSceneView<R>& sc, const Ray<R
     const ConstPrimWorld<float> wp = (ConstPrimWorld<float>)sc.wprims;
 #endif
     const ConstU32 runs = (ConstU32)sc.wruns;
-    float t_best = INFINITY;
+    float t_best = t_max;
     int32_t best = -1;
     // (d, o) pairs: N.d and N.o come out of one packed FMA chain
     const f32x2 dox = {ray.d.x, ray.o.x}, doy = {ray.d.y, ray.o.y}, doz = {ray.d.z, ray.o.z};
@@ -2488,8 +2492,8 @@ template <typename R, int MAXD, bool EXACT, bool FLAT = false, bool PF = false, 
 __device__ __forceinline__ bool trace(const DSceneView<R>& sc, const Ray<R>& wray, HitMin<R, MAXD>& hm,
                                       STKP stack, bool all = false, bool exact_wbvh = false, uint32_t pf = 0,
                                       bool xthread = false, unsigned long long* pc = nullptr,
-                                      unsigned long long* tmid = nullptr) {
-    if constexpr (MAXD == 0) return trace_world<R, MAXD, FLAT, SIG>(sc, wray, hm);
+                                      unsigned long long* tmid = nullptr, float t_max = INFINITY) {
+    if constexpr (MAXD == 0) return trace_world<R, MAXD, FLAT, SIG>(sc, wray, hm, t_max);
     else if constexpr (MAXD < 0) return trace_world_bvh<R, MAXD, FLAT, SIG>(sc, wray, hm, stack);
     else if constexpr (EXACT && sizeof(R) == 8 && SIG::exact == EXACT_SIG_SLOTS) return trace_exact_slots<R, MAXD>(sc, wray, hm);
     else if constexpr (EXACT && sizeof(R) == 8 && SIG::exact == EXACT_SIG_SLOTS_PF) {
@@ -2841,6 +2845,113 @@ template <typename R> __device__ __forceinline__ R reflectance(R cosine, R ri) {
 }
 
 // Copy the LDS-stageable scene arrays into dynamic LDS at `base` (all threads).
+// ---------------------------------------------------------------- direct light (KF_DIRECT / SHADE_DIRECT)
+// Density per solid angle of the reference's Lambertian scatter direction n + p / |p|^2 (p uniform in the unit
+// ball) at c = n.w in [-1, 1]: 3 / (4 pi) (c^2 I4 + c / 2 + I2) (scripts/pref_fit.py: the integrals, the check
+// against draws and these fits).  Not a cosine lobe: 31 / (40 pi) at c = 1, 1 / (40 pi) at c = -1, an eighth of
+// the mass below the surface.  One degree-12 polynomial per half range, in c for c >= 0 and in 1 + c below (no
+// cancellation where the density is smallest); f32 Horner against the closed form in double: <= 4.1e-7 relative.
+__device__ __forceinline__ float p_ref(float c) {
+    constexpr float POS[13] = {4.687499989e-02f, 1.193662504e-01f, 2.109346407e-01f, -3.182360321e-01f, 4.384646746e-01f,
+                               -5.650430594e-01f, 6.764583753e-01f, -7.241372258e-01f, 6.506399998e-01f, -4.540778796e-01f,
+                               2.244665963e-01f, -6.870972075e-02f, 9.688542775e-03f};
+    constexpr float NEG[13] = {7.957747214e-03f, 1.023136740e-02f, 9.095875847e-03f, 6.859471165e-03f, 5.130585021e-03f,
+                               6.035432763e-04f, 1.300812948e-02f, -3.076874430e-02f, 6.245102047e-02f, -7.877823971e-02f,
+                               6.532436274e-02f, -3.119069330e-02f, 6.950574189e-03f};
+    c = fminf(fmaxf(c, -1.0f), 1.0f);
+    const bool neg = c < 0.0f;
+    const float x = neg ? 1.0f + c : c;
+    float acc = neg ? NEG[12] : POS[12];
+#pragma unroll
+    for (int k = 11; k >= 0; --k) acc = __builtin_fmaf(acc, x, neg ? NEG[k] : POS[k]);
+    return acc;
+}
+
+// The part of that density a hit at distance r cannot use.  The scattered ray's direction d = n + q is not
+// normalised and every hit test takes t >= 0.001 only, so a surface at distance r along w is hit only when
+// |d| <= L = 1000 r; the directions' density with |d| > L is 3 / (4 pi) int_L^inf s^2 / (s^2 - 2 s c + 1)^3 ds
+// (the ball's density 3 / (4 pi |q|^6) along d = s w), = 3 / (4 pi) int_0^1 L^3 u^2 / (L^2 - 2 L c u + u^2)^3 du
+// with s = L / u: about 1 / (4 pi L^3), so it matters within a few hundredths of a light only (the Cornell box's
+// light hangs 0.002 under its ceiling).  8-point Gauss-Legendre; below L = 64 only (beyond: < 4e-5 of p_ref).
+__device__ __forceinline__ float p_ref_beyond(float c, float L) {
+    constexpr float X[4] = {0.1834346425f, 0.5255324099f, 0.7966664774f, 0.9602898565f};
+    constexpr float Wt[4] = {0.1813418917f, 0.1568533229f, 0.1111905172f, 0.0506142681f};
+    float sum = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float u = 0.5f + (k < 4 ? 0.5f : -0.5f) * X[k & 3];
+        const float den = fmaxf(__builtin_fmaf(u, u - 2.0f * L * c, L * L), 1e-12f);
+        sum += Wt[k & 3] * (u * u) * fast_rcp(den * den * den);
+    }
+    return 0.238732415f * (L * L * L) * sum;  // 3 / (4 pi)
+}
+
+// One light sample from x (shading normal n) with the block w of step PHILOX2_LIGHT_STEP0 + b + 1: the pick from
+// w.z (an 18-bit draw, the grid of DLight::cdf), the point from w.x, w.y.  Returns the shadow ray's direction
+// d = y - x (the light is at t = 1), the weight p_ref(n.w) Le W (zero when the sample counts nothing: x on or
+// inside a sphere, a degenerate direction) and the light's own primitive in this mode's order.
+template <int MAXD>
+__device__ __forceinline__ V<float> sample_light(const DSceneView<float>& sc, V<float> x, V<float> n, uint4 w,
+                                                 V<float>& weight, uint32_t& prim) {
+    const float pick = u01<float>(w.z);
+    uint32_t li = 0;
+    if (sc.n_lights <= LIGHT_SCAN_MAX) {  // the cdf words through the scalar cache (the index is wave-uniform)
+        const ConstU32 words = (ConstU32)(const void*)sc.lights;
+        for (uint32_t k = 0; k + 1u < sc.n_lights; ++k)
+            li += pick >= __uint_as_float(words[k * (uint32_t)(sizeof(DLight) / 4u) + 3u]) ? 1u : 0u;
+    } else {  // first light whose cdf exceeds the pick
+        uint32_t lo = 0, hi = sc.n_lights - 1u;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (pick < sc.lights[mid].cdf) hi = mid;
+            else lo = mid + 1u;
+        }
+        li = lo;
+    }
+    const DLight L = load16(sc.lights + li);
+    prim = MAXD < 0 ? L.prim_bvh : L.prim_list;
+    V<float> d;
+    float W;
+    if (L.kind == PRIM_SPHERE) {
+        const V<float> oc = ld3(L.p) - x;
+        const float d2 = dot(oc, oc), r2 = L.u[0] * L.u[0];
+        const float s2 = r2 * fast_rcp(d2);                                 // sin^2 theta_max
+        const float cmax = fast_sqrt(fmaxf(0.0f, 1.0f - s2));
+        const float omc = s2 * fast_rcp(1.0f + cmax);                       // 1 - cos theta_max
+        const float ct = 1.0f - u01<float>(w.x) * omc;                      // uniform in the cone
+        const float st = fast_sqrt(fmaxf(0.0f, 1.0f - ct * ct));
+        const float turn = u01<float>(w.y);
+        const float dist = fast_sqrt(d2);
+        const V<float> axis = fast_rcp(dist) * oc;
+        // a frame around the axis (Duff et al. 2017)
+        const float sg = __builtin_copysignf(1.0f, axis.z), a = -fast_rcp(sg + axis.z), bb = axis.x * axis.y * a;
+        const V<float> e1 = mk(1.0f + sg * axis.x * axis.x * a, sg * bb, -sg * axis.x);
+        const V<float> e2 = mk(bb, sg + axis.y * axis.y * a, -axis.y);
+        const V<float> dir = vfma(st * __builtin_amdgcn_cosf(turn), e1, vfma(st * __builtin_amdgcn_sinf(turn), e2, ct * axis));
+        // first intersection along dir: t = d cos - sqrt(r^2 - d^2 sin^2)
+        const float t = dist * ct - fast_sqrt(fmaxf(0.0f, r2 - d2 * (1.0f - ct * ct)));
+        d = t * dir;
+        W = d2 > r2 ? L.w * omc : 0.0f;  // (x on or inside the sphere: nothing)
+    } else {
+        float al = u01<float>(w.x), be = u01<float>(w.y);
+        if (L.kind == PRIM_TRIANGLE && al + be > 1.0f) {  // fold the far half of the parallelogram back
+            al = 1.0f - al;
+            be = 1.0f - be;
+        }
+        d = vfma(al, ld3(L.u), vfma(be, ld3(L.v), ld3(L.p))) - x;
+        const float r2 = dot(d, d);
+        W = L.w * fabsf(dot(ld3(L.n), d)) * fast_rcp(r2 * fast_sqrt(r2));  // |n_l.w| area / (r^2 P)
+    }
+    const float dl2 = dot(d, d);
+    const bool ok = dl2 > 0.0f && W > 0.0f && W < INFINITY;
+    const float c = dot(n, d) * __builtin_amdgcn_rsqf(dl2);
+    float dens = p_ref(c);
+    const float reach = 1000.0f * fast_sqrt(dl2);  // the longest scatter direction whose hit at |d| passes t >= 0.001
+    if (reach < 64.0f) dens = fmaxf(0.0f, dens - p_ref_beyond(c, reach));
+    weight = ok ? (dens * W) * ld3(L.Le) : mk(0.0f, 0.0f, 0.0f);
+    return ok ? d : n;  // (a ray that counts nothing still gets a direction every test can take)
+}
+
 template <typename R>
 __device__ __forceinline__ DSceneView<R> stage_scene(const DSceneView<R>& g, unsigned char* base, uint32_t wstride) {
     DSceneView<R> s = g;
@@ -2989,11 +3100,15 @@ constexpr int min_waves_per_simd(int kflags = 0) {
     // through the loop were spilled to VGPR lanes; the generic kernels (NoSig) keep their counts (at 7 / 8
     // they spill to scratch).  Frames identical (the waves place no work, the same loads feed the same FMAs).
     constexpr bool JIT = SIG::n > 0 || SIG::bvh != 0;
+    // the direct-light variants (KF_DIRECT, or SHADE_DIRECT passed as that bit) hold a shadow segment's normal,
+    // weight and primitive on top of the plain loop's state: one wave per SIMD fewer than the plain variant (the
+    // Cornell list kernel: 54 VGPRs plain; direct 64 with 2 spilled to scratch at 8 waves, 72 and no scratch at 7)
+    const int less = (kflags & KF_DIRECT) ? 1 : 0;
     if (sizeof(R) == 4 && MAXD < 0 && !G::uses_lds)
-        return (kflags & KF_FLAT) ? (JIT ? NRT_JIT_WBVH_WAVES : NRT_WBVH_WAVES) : NRT_WBVH_SPHERE_WAVES;
-    if (sizeof(R) == 4 && MAXD == 0 && !G::uses_lds && (kflags & KF_FLAT) && JIT) return NRT_FLAT_WAVES;
+        return ((kflags & KF_FLAT) ? (JIT ? NRT_JIT_WBVH_WAVES : NRT_WBVH_WAVES) : NRT_WBVH_SPHERE_WAVES) - less;
+    if (sizeof(R) == 4 && MAXD == 0 && !G::uses_lds && (kflags & KF_FLAT) && JIT) return NRT_FLAT_WAVES - less;
     if (sizeof(R) == 4 && MAXD == 0 && !G::uses_lds && !(kflags & KF_PERLIN))
-        return JIT ? NRT_JIT_LIST_WAVES : NRT_WORLD_LIST_WAVES;
+        return (JIT ? NRT_JIT_LIST_WAVES : NRT_WORLD_LIST_WAVES) - less;
     return 1;
 }
 static_assert(BLOCK % 64 == 0, "stack / ring / accumulator layouts assume whole waves");
@@ -3056,12 +3171,16 @@ template <> struct StackEntry<true> { using type = uint16_t; };
 // cases, whose cameras are off the origin, catch a reordering).
 template <typename R, class G, int MAXD, bool EXACT, bool LDS_SCENE, int KFLAGS = 0, class SIG = NoSig,
           class SHADE = ShadeAny>
-__global__ void __launch_bounds__(BLOCK, (min_waves_per_simd<R, G, MAXD, SIG>(KFLAGS)))
+__global__ void __launch_bounds__(BLOCK, (min_waves_per_simd<R, G, MAXD, SIG>(KFLAGS | (SHADE::direct ? KF_DIRECT : 0))))
 render_kernel(const RenderParams p, const DSceneView<R> gsc) {
     constexpr bool PROF = (KFLAGS & KF_PROF) != 0;
     constexpr bool PERLIN = (KFLAGS & KF_PERLIN) != 0;
     constexpr bool FLAT = (KFLAGS & KF_FLAT) != 0;
     static_assert(!FLAT || (MAXD <= 0 && !PERLIN), "KF_FLAT is a world-list / world-BVH variant");
+    // the Philox loop with light samples and shadow segments (nrt_render_opts.direct_light)
+    constexpr bool DIRECT = (KFLAGS & KF_DIRECT) != 0 || SHADE::direct;
+    static_assert(!DIRECT || (sizeof(R) == 4 && MAXD <= 0 && !EXACT && !G::exact_stream),
+                  "direct light: the f32 Philox world modes");
     // ChaCha8 persistent-lane loop (MAXD >= 0): the rejection samplers run where the wave is converged
     // and refill every lane with room (rejection_wave) instead of the loop head's top-up, for the
     // plane-only exact variants and the f32 kernels: C5 f64 191.3 -> 187.5 ms, C5 f32 65.8 -> 63.6 ms;
@@ -3102,7 +3221,7 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
     if constexpr (LDS_SCENE) sc = stage_scene(gsc, lds + ring_bytes + acc_bytes + stack_bytes, wprim_lds_stride(MAXD));
 
     G g;
-    constexpr bool CAM_RELOAD = NRT_CAM_RELOAD || (sizeof(R) == 4 && min_waves_per_simd<R, G, MAXD, SIG>(KFLAGS) >= 7);
+    constexpr bool CAM_RELOAD = NRT_CAM_RELOAD || (sizeof(R) == 4 && min_waves_per_simd<R, G, MAXD, SIG>(KFLAGS | (SHADE::direct ? KF_DIRECT : 0)) >= 7);
     // Camera vectors (camera.rs:205-227) q = 0..6: top_left, delta_u, delta_v, look_from,
     // disk_u, disk_v, background (f32: the host-rounded copies, kernel arguments in SGPRs)
     auto cam = [&](int q) -> V<R> {
@@ -3115,6 +3234,7 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
 
     uint32_t b = 0;  // bounces of this path
     bool bounced = false;
+    bool direct = false;  // DIRECT: the vertex this ray left took a light sample (a light hit by chance adds nothing)
     Ray<R> ray;
     V<R> tp = mk(R(1), R(1), R(1));
     uint4 w = make_uint4(0u, 0u, 0u, 0u);  // Philox: this segment's block
@@ -3167,6 +3287,9 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             if (m.kind == MAT_DIFFUSE_LIGHT) {  // emit (diffuse_light.rs:62-75), no scatter
                 const R k = bounced ? m.param : R(1.0);
                 contrib = tp * (k * albedo(m, h));
+                if constexpr (DIRECT) {
+                    if (direct) contrib = mk(R(0), R(0), R(0));  // counted by the light sample of the last vertex
+                }
                 return false;
             }
         }
@@ -3726,6 +3849,15 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
         uint32_t pxy = 0;                   // this path's pixel, x | y << 16
         bool alive = false;                 // the lane holds a path
         bool killed = false;                // absorbed by a metal (or padding): black, ends at the next shading step
+        // DIRECT: a lane's segment is an ordinary ray or a shadow ray (`shadow`) towards the light point its last
+        // Lambertian hit sampled.  The shadow segment's shading step adds tp * sweight when the closest hit is the
+        // light's own primitive (sprim), then rebuilds the scatter ray from the saved normal and the unchanged
+        // scatter block (pixel, sample, b + 1): counter-based draws, so no RNG state is saved across the segment.
+        // a shadow ray's light is at t = 1 (its direction is y - x): the query ends just past it
+        constexpr float SHADOW_T_MAX = 1.0f + 0x1p-10f;
+        bool shadow = false;
+        V<R> snormal = mk(R(0), R(0), R(0)), sweight = mk(R(0), R(0), R(0));
+        uint32_t sprim = 0;
         auto pixel_index = [&]() { return (pxy >> 16) * p.width + (pxy & 0xFFFFu); };  // RNG stream (camera.rs:320-323)
 
         // Camera::get_ray (camera.rs:244-267) for sample `cur` of pixel pxy; w holds its
@@ -3763,11 +3895,15 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             b = 0;
             bounced = false;  // Ray::bounce flag (Q4): 0 for camera rays
             killed = false;
+            if constexpr (DIRECT) direct = false;
         };
 
         WbvhTrav ts{WBVH_DONE, WBVH_NO_LEAF, 0u, INFINITY, -1, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         auto begin = [&]() {  // world-BVH mode; depth cap / absorbed: no query (Q6)
             if constexpr (MAXD < 0) wbvh_begin(ts, (!killed && b < p.max_bounces) ? wbvh_root(gsc) : WBVH_DONE, ray);
+            if constexpr (MAXD < 0 && DIRECT) {
+                if (shadow) ts.t_best = SHADOW_T_MAX;  // boxes and primitives beyond the light are culled
+            }
         };
         const uint32_t wait_min = p.wave_wait ? p.wave_wait : 1u;
 
@@ -3841,7 +3977,11 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
                 sh = alive;
                 traced = alive && !killed && b < p.max_bounces;  // depth cap returns black (Q6)
                 // world list: the global tables through the scalar cache; records read LDS
-                if (traced)
+                if constexpr (DIRECT) {
+                    if (traced)
+                        hit = trace<R, MAXD, EXACT, FLAT, false, SIG>(gsc, ray, hm, stack, false, false, 0u, false, nullptr,
+                                                                       nullptr, shadow ? SHADOW_T_MAX : INFINITY);
+                } else if (traced)
                     hit = trace<R, MAXD, EXACT, FLAT, false, SIG>(MAXD == 0 ? gsc : sc, ray, hm, stack,
                                                                    p.exact_all != 0, p.exact_wbvh != 0, 0u,
                                                                    p.exact_thread != 0);
@@ -3852,11 +3992,23 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             MatV<R> m;
             V<R> contrib;  // (set by surface() wherever it is read: ends implies sh)
             bool scatter = false;
-            if (sh) scatter = surface(traced, hit, hm, h, m, contrib);
+            bool sseg = false;  // DIRECT: this lane shades a shadow segment
+            if constexpr (DIRECT) {
+                sseg = sh && shadow;
+                if (sseg) {  // visible iff the closest hit is the sampled light's own record
+                    const bool visible = hit && hm.prim == sprim;
+                    contrib = visible ? tp * sweight : mk(R(0), R(0), R(0));
+                } else if (sh) {
+                    scatter = surface(traced, hit, hm, h, m, contrib);
+                }
+            } else {
+                if (sh) scatter = surface(traced, hit, hm, h, m, contrib);
+            }
             const unsigned long long t2 = stamp();
 
             // finished samples: radiance into the pixel's LDS sum, completion counts per slot
-            const bool ends = sh && !scatter;
+            // (DIRECT: a shadow segment's light adds to the sum mid-path, on the same grid; its sample does not end)
+            const bool ends = sh && !scatter && !sseg;
             auto lit = [&]() {  // some component is not +-0 (a NaN counts, as with !=)
                 if constexpr (NRT_CONTRIB_BITS && sizeof(R) == 4) {
                     // every bit below the sign, of the three words at once: one compare instead of three and two ORs
@@ -3866,7 +4018,7 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
                     return contrib.x != R(0) || contrib.y != R(0) || contrib.z != R(0);
                 }
             };
-            if (ends && lit()) {
+            if ((ends || sseg) && lit()) {
                 double* a = acc + (slot * P + j) * 3u;
                 if constexpr (sizeof(R) == 4) {  // 2^k scaling and rint exact in f32 (host: k in range)
                     atomicAdd(a, (double)__builtin_rintf(contrib.x * p.acc_scale_f));
@@ -3923,9 +4075,34 @@ render_kernel(const RenderParams p, const DSceneView<R> gsc) {
             }
             // this segment's block: the scatter's (pixel, sample, bounce + 1) or the
             // claimed sample's camera block (pixel', sample', 0)
-            w = G::template block_at<R>(pixel_index(), cur, scatter ? b + 1u : 0u);
+            w = G::template block_at<R>(pixel_index(), cur, (scatter || sseg) ? b + 1u : 0u);
             const unsigned long long t3 = stamp();
-            if constexpr (SHADE::has(MAT_METAL)) {
+            if constexpr (DIRECT) {
+                if (sseg) {  // Lambertian scatter from the saved normal (scatter_ray's arm; the origin is h.p already)
+                    V<R> dir = snormal + unit_ball_inverse<R>(w.x, w.y, w.z);
+                    if (fabs(dir.x) < R(1e-8) && fabs(dir.y) < R(1e-8) && fabs(dir.z) < R(1e-8)) dir = snormal;
+                    ray.d = dir;
+                    bounced = true;
+                    ++b;
+                    direct = true;
+                    shadow = false;
+                } else if (scatter) {
+                    // a Lambertian hit whose shadow ray would not be the ray at the depth cap (Q6) takes a light sample
+                    bool sample = SHADE::has(MAT_LAMBERTIAN) && b + 1u < p.max_bounces;
+                    if constexpr (SHADE::has(MAT_METAL) || SHADE::has(MAT_DIELECTRIC)) sample = sample && m.kind == MAT_LAMBERTIAN;
+                    if (sample) {
+                        const uint4 wl = G::template block_at<R>(pixel_index(), cur, PHILOX2_LIGHT_STEP0 + b + 1u);
+                        tp = tp * albedo(m, h);
+                        snormal = h.n;
+                        ray.o = h.p;
+                        ray.d = sample_light<MAXD>(gsc, h.p, h.n, wl, sweight, sprim);
+                        shadow = true;
+                    } else {
+                        direct = false;
+                        if (!scatter_ray(h)) killed = true;
+                    }
+                }
+            } else if constexpr (SHADE::has(MAT_METAL)) {
                 if (scatter && !scatter_ray(h)) killed = true;
             } else {  // only a metal absorbs
                 if (scatter) scatter_ray(h);

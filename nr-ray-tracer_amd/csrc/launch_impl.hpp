@@ -159,6 +159,23 @@ static void launch_one(const RenderParams& p, const DSceneView<R>& v, bool perli
     using dev::KF_PERLIN;
     using dev::KF_PROF;
     constexpr bool FLAT_MODE = MAXD <= 0 && sizeof(R) == 4;  // KF_FLAT: f32 world list / world BVH
+    if constexpr (FLAT_MODE && !G::exact_stream) {
+        if (p.direct_light) {  // the Philox loop with shadow segments (KF_DIRECT; the light table stays in HBM)
+            using dev::KF_DIRECT;
+            const bool staged = scene <= LDS_SCENE_LIMIT;
+            if (flat && !perlin) {
+                if (staged) launch_variant<R, G, MAXD, EXACT, true, KF_FLAT | KF_DIRECT>(p, v, ring + scene, stream);
+                else launch_variant<R, G, MAXD, EXACT, false, KF_FLAT | KF_DIRECT>(p, v, ring, stream);
+            } else if (perlin) {
+                if (staged) launch_variant<R, G, MAXD, EXACT, true, KF_PERLIN | KF_DIRECT>(p, v, ring + scene, stream);
+                else launch_variant<R, G, MAXD, EXACT, false, KF_PERLIN | KF_DIRECT>(p, v, ring, stream);
+            } else {
+                if (staged) launch_variant<R, G, MAXD, EXACT, true, KF_DIRECT>(p, v, ring + scene, stream);
+                else launch_variant<R, G, MAXD, EXACT, false, KF_DIRECT>(p, v, ring, stream);
+            }
+            return;
+        }
+    }
     if constexpr (FLAT_MODE) {
         if (flat && !perlin) {  // the phase profile measures this same variant
             if (p.counters) {

@@ -109,6 +109,7 @@ DeviceScene* gpu_upload_scene(const FlatScene& fs, int device) {
         auto* wb4c = (DBvh4cNode*)track(upload(fs.wbvh.nodes4c, "wbvh4c"), fs.wbvh.nodes4c.size() * sizeof(DBvh4cNode));
         auto* wbp = (DPrimWorld<float>*)track(upload(f32.wbvh_prims, "wbvh_prims"),
                                               f32.wbvh_prims.size() * sizeof(DPrimWorld<float>));
+        auto* lts = (DLight*)track(upload(fs.lights, "lights"), fs.lights.size() * sizeof(DLight));
         const uint32_t np = (uint32_t)fs.prims.size(), nx = (uint32_t)fs.xforms.size(),
                        ni = (uint32_t)fs.instances.size(), nm = (uint32_t)fs.materials.size(),
                        nt = (uint32_t)fs.textures.size();
@@ -143,7 +144,7 @@ DeviceScene* gpu_upload_scene(const FlatScene& fs, int device) {
                                      wx_ok ? (uint32_t)xt.nodes.size() : 0u,
                                      std::max<uint32_t>(1u, x4 ? xt.stack4 : xt.depth), wx_ok ? xth : nullptr,
                                      wx_ok ? xt.threaded_n : 0u, wx_ok ? wx : nullptr,
-                                     wx_ok ? wxp : nullptr, wx_ok ? (uint32_t)fs.wexact.size() : 0u, 0u};
+                                     wx_ok ? wxp : nullptr, wx_ok ? (uint32_t)fs.wexact.size() : 0u, 0u, nullptr, 0u};
         {  // small culling trees travel into LDS with the scene (knob NRT_EXACT_XSTAGE=0: read from HBM)
             const size_t xb = xt.nodes4c.size() * sizeof(DBvh4cNode) +
                               fs.wexact.size() * (sizeof(DPrimWorld<float>) + sizeof(DExactRef));
@@ -158,7 +159,8 @@ DeviceScene* gpu_upload_scene(const FlatScene& fs, int device) {
                                     (uint32_t)fs.mats_fast.size(), wpr, (uint32_t)f32.wprims.size(), wrn,
                                     (uint32_t)fs.wruns.size(), fs.wflags, wbn, use_wbvh4(fs) ? wb4 : nullptr,
                                     use_wbvh4(fs) ? wb4c : nullptr, fs.wbvh.root4, fs.wbvh.root,
-                                    (uint32_t)fs.wbvh.nodes.size(), wstack, nullptr, 0u, nullptr, nullptr, 0u, 0u};
+                                    (uint32_t)fs.wbvh.nodes.size(), wstack, nullptr, 0u, nullptr, nullptr, 0u, 0u, lts,
+                                    (uint32_t)fs.lights.size()};
         ds->wbvh_ok = fs.wbvh_ok && fs.wbvh_f32_ok;  // (the f32 world-BVH modes)
         for (const DTexture& t : fs.textures) ds->perlin |= t.kind == TEX_NOISE || t.kind == TEX_MARBLE;
         ds->planes = !fs.prims.empty();
@@ -295,6 +297,8 @@ void gpu_launch_render(const DeviceScene* ds, const RenderParams& p, uint32_t pr
     else {
         const int maxd = gpu_fast_maxd(ds, trace);
         const DSceneView<float> v = mode_view(ds, maxd);
+        if (q.direct_light && (rng != RNG_PHILOX || maxd > 0 || v.n_lights == 0 || q.counters))  // (the API's checks: api.cpp)
+            throw std::runtime_error("direct_light: outside the accelerated path (f32 Philox world modes with lights)");
         // scene-specialised kernel (jit.hip): the world list's run words, or the world BVH's
         // width and tie flag, as template arguments; the same LDS layout as launch_one
         void* jit = nullptr;
@@ -314,7 +318,8 @@ void gpu_launch_render(const DeviceScene* ds, const RenderParams& p, uint32_t pr
             // camera's mode at run time (one variant per scene)
             const uint32_t cam_sig = rng == RNG_PHILOX ? (q.defocus ? dev::SHADE_DEFOCUS : 0u) | (q.spp > 1u ? dev::SHADE_MULTI : 0u) |
                                                              (q.sample0 ? dev::SHADE_WINDOW : 0u) |
-                                                             (q.pixel_list ? dev::SHADE_LIST : 0u)
+                                                             (q.pixel_list ? dev::SHADE_LIST : 0u) |
+                                                             (q.direct_light ? dev::SHADE_DIRECT : 0u)
                                                        : dev::SHADE_CAM_RUNTIME;
             const std::string shade = ", nrt::dev::ShadeSig<" + std::to_string(ds->mat_kinds) + "u, " + std::to_string(cam_sig) + "u>";
             if (maxd == MODE_WORLD_LIST) {

@@ -16,18 +16,27 @@ enum : uint32_t { RNG_CHACHA8 = 0, RNG_PHILOX = 1, RNG_PHILOX2_BLOCK = 2 /* nrt_
 // spp <= 2^24 and steps 0..255 (camera 0, scatters 1..max_bounces, defocus 255).
 constexpr uint32_t PHILOX2_STEPS = 256, PHILOX2_MAX_SPP = 1u << 24;
 constexpr uint32_t PHILOX2_MAX_BOUNCES = PHILOX2_STEPS - 2u;
+// Step map of the f32 blocks: 0 the camera ray; 1 .. 126 (.. 254 without direct_light) the scatter at bounce b =
+// step - 1; 128 .. 253 with direct_light the light sample at bounce b = step - 128 (PHILOX2_LIGHT_STEP0 + b + 1:
+// pick, and the two coordinates of the point); 255 the defocus disk.  The light steps start above the scatter
+// steps a direct_light render may use, so it takes at most PHILOX2_DIRECT_MAX_BOUNCES bounces.
+constexpr uint32_t PHILOX2_LIGHT_STEP0 = 127, PHILOX2_DIRECT_MAX_BOUNCES = 126;
 
 namespace dev {
 // Kernel variant flags (render_kernel's KFLAGS): KF_PROF = phase-profile stamps (diagnostics),
 // KF_PERLIN = the scene has Noise / Marble textures, KF_FLAT = world-mode scene without spheres
 // whose materials all have solid colours, KF_PLANES = f64 kernel, no spheres, KF_TEXPAL = every
 // texture is a solid colour or a PAL16 image (scene-specialised kernels only) (kernel.hpp).
-constexpr int KF_PROF = 1, KF_PERLIN = 2, KF_FLAT = 4, KF_PLANES = 8, KF_TEXPAL = 16;
+// KF_DIRECT = the Philox loop's direct-light variant (nrt_render_opts.direct_light; generic kernels: the
+// scene-specialised ones carry SHADE_DIRECT instead).
+constexpr int KF_PROF = 1, KF_PERLIN = 2, KF_FLAT = 4, KF_PLANES = 8, KF_TEXPAL = 16, KF_DIRECT = 32;
 // Camera-mode bits of a scene-specialised kernel's shading signature (kernel.hpp ShadeSig<MATS, CAM>):
 // a non-zero defocus disk, spp > 1, or the mode read from RenderParams at run time; SHADE_WINDOW: the launch's
 // sample window starts past 0 (RenderParams::sample0: without the bit the kernel never reads it); SHADE_LIST: the
-// launch's pixels come from a list (RenderParams::pixel_list, read under the same rule).
-constexpr uint32_t SHADE_DEFOCUS = 1u, SHADE_MULTI = 2u, SHADE_CAM_RUNTIME = 4u, SHADE_WINDOW = 8u, SHADE_LIST = 16u;
+// launch's pixels come from a list (RenderParams::pixel_list, read under the same rule); SHADE_DIRECT: a
+// direct_light launch (RenderParams::direct_light: the loop with shadow segments, kernel.hpp).
+constexpr uint32_t SHADE_DEFOCUS = 1u, SHADE_MULTI = 2u, SHADE_CAM_RUNTIME = 4u, SHADE_WINDOW = 8u, SHADE_LIST = 16u,
+                   SHADE_DIRECT = 32u;
 // Exact kernel, small scenes: at most this many slots of the culling tree are tested in slot order
 // instead of walked (EXACT_SIG_SLOTS / EXACT_SIG_SLOTS_PF; host default and launcher share it)
 constexpr uint32_t EXACT_SLOTS_MAX = 32;
@@ -112,6 +121,9 @@ struct RenderParams {
     // and writes it to out + 3 (pixel_begin + k): a compact (n, 3) array in list order.  nullptr: the launch's
     // pixels are the rectangle's (kernel.hpp fetch; a scene-specialised kernel reads it only with SHADE_LIST)
     const uint32_t* pixel_list;
+    // f32 Philox, world modes: sample the scene's lights at every Lambertian hit (nrt_render_opts.direct_light; the
+    // host clears it for a scene without lights).  Picks the kernel variant (KF_DIRECT / SHADE_DIRECT): no kernel reads it.
+    uint32_t direct_light;
 };
 
 }  // namespace nrt

@@ -62,7 +62,8 @@ class _Camera(C.Structure):
 
 class _RenderOpts(C.Structure):
     _fields_ = [("precision", C.c_uint32), ("rng", C.c_uint32), ("device", C.c_int32), ("row_offset", C.c_uint32),
-                ("row_stride", C.c_uint32), ("trace", C.c_uint32), ("gpus", C.c_uint32), ("sample_offset", C.c_uint32)]
+                ("row_stride", C.c_uint32), ("trace", C.c_uint32), ("gpus", C.c_uint32), ("sample_offset", C.c_uint32),
+                ("direct_light", C.c_uint32)]
 
 
 class _SceneStats(C.Structure):
@@ -70,7 +71,7 @@ class _SceneStats(C.Structure):
                 ("materials", C.c_uint64), ("textures", C.c_uint64), ("texels", C.c_uint64), ("trees", C.c_uint32),
                 ("max_instance_depth", C.c_uint32), ("device_bytes", C.c_uint64), ("world_prims", C.c_uint64),
                 ("coplanar_pairs", C.c_uint32), ("world_list_ok", C.c_uint32), ("exact_mode", C.c_uint32),
-                ("texel_formats", C.c_uint32), ("texel_bytes", C.c_uint64)]
+                ("texel_formats", C.c_uint32), ("texel_bytes", C.c_uint64), ("lights", C.c_uint32)]
 
 
 class _DenoiseOpts(C.Structure):
@@ -397,7 +398,7 @@ class CameraBuilder:
 
 
 def _opts(precision: str, rng: str, device: int, row_offset: int, row_stride: int,
-          trace: str = "auto", gpus: int = 0, sample_offset: int = 0) -> _RenderOpts:
+          trace: str = "auto", gpus: int = 0, sample_offset: int = 0, direct_light: bool = False) -> _RenderOpts:
     if precision not in PRECISION:
         raise ValueError(f"precision must be one of {list(PRECISION)}")
     if rng not in RNG:
@@ -411,6 +412,7 @@ def _opts(precision: str, rng: str, device: int, row_offset: int, row_stride: in
     if not 0 <= sample_offset < 1 << 32:
         raise NrtError(-1, f"sample_offset {sample_offset} is not in 0 .. 2^32 - 1")
     o.sample_offset = sample_offset
+    o.direct_light = 1 if direct_light else 0
     return o
 
 
@@ -466,11 +468,14 @@ class Scene:
     def render(self, camera: Optional[Camera] = None, precision: str = "f64", rng: str = "chacha8",
                device: int = -1, row_offset: int = 0, row_stride: int = 1,
                progress: Optional[Callable[[int], None]] = None, trace: str = "auto", gpus: int = 0,
-               denoise=False, sample_offset: int = 0, variance_out: Optional[np.ndarray] = None) -> np.ndarray:
+               denoise=False, sample_offset: int = 0, variance_out: Optional[np.ndarray] = None,
+               direct_light: bool = False) -> np.ndarray:
         """Camera::render -> Rgb32FImage as float32 array (rows, W, 3).  gpus = N >= 1: the whole frame
         over devices device .. device+N-1 (device -1: 0), one RCCL gather (nrt_render_opts.gpus).
         sample_offset = s0 (rng "philox"): samples s0 .. s0 + spp - 1 of every pixel instead of 0 .. spp - 1
         (nrt_render_opts.sample_offset): frames of disjoint windows have independent noise.
+        direct_light = True (f32, "philox", the world modes): one light sample and shadow ray at every Lambertian hit
+        (nrt_render_opts.direct_light); the same expected frame with less noise where lights are small.
         denoise = True (or the number of passes, 1..5): the frame, then its feature buffers
         (render_aov), then the a-trous filter (nrt.denoise) over both; whole frames on one device.
         denoise = "variance": the same chain with the variance-guided filter (nrt.denoise_vg).
@@ -492,7 +497,8 @@ class Scene:
         if denoise:
             if row_stride > 1 or row_offset:
                 raise ValueError("denoise filters whole frames: row_offset 0 and row_stride 1")
-            kw = dict(precision=precision, rng=rng, device=device, progress=progress, trace=trace, gpus=gpus)
+            kw = dict(precision=precision, rng=rng, device=device, progress=progress, trace=trace, gpus=gpus,
+                      direct_light=direct_light)
             if denoise == "dual":
                 half = cam.samples_per_pixel // 2
                 if cam.samples_per_pixel % 2 or half < 2:
@@ -509,7 +515,7 @@ class Scene:
                 return denoise_vg(frame, device=device, out=frame, variance_out=variance_out, **aov)
             return globals()["denoise"](frame, iterations=5 if denoise is True else int(denoise), device=device,
                                         out=frame, **aov)
-        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset)
+        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset, direct_light)
         rows = lib().nrt_rows_selected(cam.height, C.byref(o))
         out = np.empty((rows, cam.width, 3), dtype=np.float32)
         cb = PROGRESS_FN(lambda _u, n: progress(n)) if progress else PROGRESS_FN()
@@ -519,15 +525,15 @@ class Scene:
 
     def render_pixels(self, pixels, camera: Optional[Camera] = None, precision: str = "f32", device: int = -1,
                       trace: str = "auto", sample_offset: int = 0, rng: str = "philox", row_offset: int = 0,
-                      row_stride: int = 1, gpus: int = 0) -> np.ndarray:
+                      row_stride: int = 1, gpus: int = 0, direct_light: bool = False) -> np.ndarray:
         """The pixels of linear indices y * W + x in `pixels`, as (n, 3) float32 in list order (nrt_render_pixels):
-        row k is, bit for bit, pixel pixels[k] of render(...) with the same camera, precision, trace and
-        sample_offset.  Philox, whole frames, one device: another rng, a row subset or gpus >= 1 is an invalid
+        row k is, bit for bit, pixel pixels[k] of render(...) with the same camera, precision, trace, sample_offset
+        and direct_light.  Philox, whole frames, one device: another rng, a row subset or gpus >= 1 is an invalid
         argument, as is an index >= W * H."""
         cam = camera or self.camera
         if cam is None:
             raise ValueError("no camera")
-        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset)
+        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset, direct_light)
         px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
         out = np.empty((px.size, 3), dtype=np.float32)
         _check(lib().nrt_render_pixels(self._h, C.byref(cam._c()), C.byref(o), px.ctypes.data_as(C.POINTER(C.c_uint32)),
@@ -547,16 +553,17 @@ class Scene:
                         precision: str = "f32", device: int = -1, trace: str = "auto", sample_offset: int = 0,
                         samples_out: Optional[np.ndarray] = None, halves_out=None, rng: str = "philox",
                         row_offset: int = 0, row_stride: int = 1, gpus: int = 0, sigma_normal: float = 0.3,
-                        sigma_depth: float = 0.5) -> np.ndarray:
+                        sigma_depth: float = 0.5, direct_light: bool = False) -> np.ndarray:
         """Adaptive sampling (nrt_render_adaptive): every pixel gets min_samples samples (0: max(4, spp / 8)), then
         the pixels whose estimated relative error is not below `threshold` double theirs, level by level, up to the
         camera's samples_per_pixel.  Returns the (H, W, 3) float32 frame.  samples_out: an (H, W) uint32 array for
         the samples each pixel drew.  halves_out: a pair of (H, W, 3) float32 arrays for the two half-sample frames
-        A, B (the frame is their mean; nrt.denoise_vg_dual accepts them)."""
+        A, B (the frame is their mean; nrt.denoise_vg_dual accepts them).  direct_light: every launch of the loop
+        samples the lights (render's direct_light)."""
         cam = camera or self.camera
         if cam is None:
             raise ValueError("no camera")
-        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset)
+        o = _opts(precision, rng, device, row_offset, row_stride, trace, gpus, sample_offset, direct_light)
         a = _AdaptiveOpts(threshold, min_samples, sigma_normal, sigma_depth)
         out = np.empty((cam.height, cam.width, 3), dtype=np.float32)
         if samples_out is not None and (samples_out.dtype != np.uint32 or not samples_out.flags.c_contiguous or
